@@ -26,6 +26,31 @@ sys.path.insert(0, ROOT)
 PEAK_MFMA_FP8_TFLOPS = 5000.0    # dense fp8 (MX K = 128 measured 4647 TF), same table
 PEAK_MFMA_BF16_TFLOPS = 2500.0   # dense, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 PEAK_HBM_GBS = 8000.0
+DUMP_BUDGET = 64 << 20           # --dump-outputs: bytes written in all
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy, float32 (float64 for integer arrays such as token ids).  An array that does not fit
+    what is left of DUMP_BUDGET is cut to a fixed, seeded sample of its rows (same rows on every run of the same shape); the row indices go
+    beside it as <name>_rows.npy.  Returns {name: shape written}."""
+    import numpy as np
+    left, shapes = DUMP_BUDGET - 4096 * (2 * len(arrays)), {}          # (room for the .npy headers)
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):      # smallest first: only the largest is ever sampled
+        a = t.detach().cpu()
+        a = a.double().numpy() if not torch.is_floating_point(a) else a.float().numpy()
+        if a.nbytes > left and a.ndim >= 1 and a.shape[0] > 1:
+            row = a.nbytes // a.shape[0]
+            n = max(1, min(a.shape[0], (left - 8 * a.shape[0]) // (row + 8)))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=n, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+        if a.nbytes > left:
+            raise SystemExit(f"--dump-outputs: {name} {a.shape} does not fit the {DUMP_BUDGET >> 20} MB budget")
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def algorithmic_tflop(cfg, T, S_text=100):
@@ -189,7 +214,15 @@ def main():
     ap.add_argument("--stage-flags", type=int, default=0, help="experiment controls of the stage-level calls (include/vl2hip.h VL2_STAGE_*: 1 persistent GEMM, "
                     "2 no mixed launch, 4 in-GEMM statistics reduction (ViT), 8 fused decode attention); travel in the call descriptors")
     ap.add_argument("--tune", type=str, default="", help="debug: comma list of gemm=<variant>, splitk=<0|1>, attn=<variant> (videollama2_amd/ops.py launch controls)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         f"{DUMP_BUDGET >> 20} MB in all): the spliced inputs_embeds, the prefill logits, the greedy tokens and the logits "
+                         "after the last decode step.  Inputs are seeded, so two builds run with the same arguments compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -253,7 +286,7 @@ def main():
     ev = lambda: torch.cuda.Event(enable_timing=True)
     graph = None
 
-    def step(rec=None):
+    def step(rec=None, keep=None):
         e = [ev() for _ in range(4)]
         e[0].record()
         _, _, _, emb, _ = model.prepare_inputs_labels_for_multimodal(ids, mask, None, None, [(frames, "video")])
@@ -261,18 +294,24 @@ def main():
         dec = model.decoder
         dec.prefill(emb[0])                          # logits of the last position -> dec.logits
         e[2].record()
+        if keep is not None:                         # --dump-outputs, last timed step: what the decode below overwrites
+            keep["inputs_embeds"] = emb[0]
+            keep["prefill_logits"] = dec.logits.clone()
         if graph is not None:                        # one captured hipGraph per token: argmax + the whole decode step
             dec.state.copy_(torch.tensor([dec.pos - 1, 0], dtype=torch.int32), non_blocking=True)
             for s in range(n_new):                   # fixed length: stop criteria disabled for timing
-                graph.replay()
+                graph.replay()                       # (the argmax leaves the token in dec.hist[s])
             dec.pos += n_new
         else:
             for s in range(n_new):
-                ops.argmax(dec.logits, dec.tok)
+                ops.argmax(dec.logits, dec.tok, dec.hist, s)
                 dec.decode_step()
         e[3].record()
         if rec is not None:
             rec.append(e)
+        if keep is not None:
+            keep["tokens"] = dec.hist[:n_new].clone()
+            keep["logits"] = dec.logits.clone()
         return emb.shape[1]
 
     S = step()                                       # eager pass (also performs every first-launch initialisation)
@@ -301,14 +340,16 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     rec = []
+    kept = {} if args.dump_outputs and rank == 0 else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        S = step(rec)
+    for i in range(args.steps):
+        S = step(rec, kept if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, kept) if kept is not None else None      # before the passes below reuse the buffers
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -659,6 +700,8 @@ def main():
             out["batched_decode"] = batched
         if bprefill is not None:
             out["batched_prefill"] = bprefill
+        if dumped is not None:
+            out["dumped_outputs"] = dict(dir=args.dump_outputs, shapes=dumped)
         if not args.no_cpu_baseline and world == 1:          # the CPU leg is reported at N=1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(min(os.cpu_count() or 1, 32), T, S)   # eager torch oversubscribes badly beyond ~32 threads

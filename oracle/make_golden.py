@@ -76,9 +76,42 @@ def mint_small(T=4, n_new=8, cfg=None, fname="small_T4.pt"):
     print("wrote", fname, ";", {k: (tuple(v.shape) if torch.is_tensor(v) else type(v).__name__) for k, v in g.items()})
 
 
+def mint_reference_checks(fname="reference_checks.pt"):
+    """What the reference itself returns in the cross-checks of tests/test_oracle_pin.py (`*_matches_live_reference`: unrounded
+    seeded weights, encode + 5 greedy tokens per family) and tests/test_emu_pipeline.py (padded-batch test: the reference's own
+    batch-2 generate), on the same seeded inputs those tests build, so that they run without the reference tree."""
+    g = {}
+    for fam, cfg, seed, rseed in (("v2", O.config_small(4), 77, 5), ("v21", O.config_small_v21(4), 78, 6)):
+        model, _ = RH.build_reference_model(cfg)
+        RH.reseed_weights(model, seed)
+        norm = O.normalise_frames_u8_siglip if fam == "v21" else O.normalise_frames_u8
+        rng = np.random.default_rng(rseed)
+        fr = norm(rng.integers(0, 256, (4, 56, 56, 3), dtype=np.uint8))
+        with torch.no_grad():
+            enc = model.encode_images_or_videos([(fr, "video")])
+            ids = torch.tensor([1] + list(rng.integers(3, 512, 5)) + [-201] + list(rng.integers(3, 512, 4)))
+            out = model.generate(ids[None], attention_mask=torch.ones_like(ids)[None], images=[(fr, "video")], do_sample=False,
+                                 max_new_tokens=5, use_cache=True, pad_token_id=0, eos_token_id=None)
+        g[fam] = dict(seed=seed, frames_seed=rseed, state_dict_keys=sorted(k for k, v in model.state_dict().items() if torch.is_floating_point(v)),
+                      encode=enc.clone(), tokens=out[0].tolist())
+    gs = torch.load(os.path.join(OUT, "small_T4.pt"), weights_only=False)
+    model, _ = RH.build_reference_model(gs["cfg"])
+    RH.reseed_weights(model, gs["seed"])
+    images = [(gs["frames"], "video"), (torch.flip(gs["frames"], dims=[0]).contiguous(), "video")]
+    both = torch.stack([gs["input_ids"], gs["input_ids"]])
+    with torch.no_grad():
+        ref = model.generate(both, attention_mask=torch.ones_like(both), images=images, do_sample=False, max_new_tokens=3, use_cache=True,
+                             pad_token_id=0, eos_token_id=None)
+    g["v2_batch2_flipped_tokens"] = ref.tolist()
+    torch.save(g, os.path.join(OUT, fname))
+    print("wrote", fname, ";", {k: (v["tokens"] if isinstance(v, dict) else v) for k, v in g.items()})
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["v2", "v21"]
+    which = sys.argv[1:] or ["v2", "v21", "checks"]
     if "v2" in which:
         mint_small()
     if "v21" in which:      # VideoLLaMA2.1 family: SigLIP tower + stc_connector_v35 + Qwen2 (SURVEY 8f row 1)
         mint_small(cfg=O.config_small_v21(4), fname="small_v21_T4.pt")
+    if "checks" in which:
+        mint_reference_checks()

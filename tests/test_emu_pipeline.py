@@ -3,6 +3,8 @@ the host against tests/emu/hip_emu.h (fibers + emulated MFMA / LDS-DMA / shuffle
 and the unmodified videollama2_amd host layer runs the small config end to end against the reference goldens.
 This guards kernel indexing logic (swizzles, fragment maps, edge rows) where no GPU exists; the `-m gpu` tests are
 the parity tests proper."""
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -10,6 +12,8 @@ import torch.nn.functional as F
 from oracle import vl2_oracle as O
 from tests.emu.backend import emulated_backend
 from tests.util import TOL_BF16_OUT, TOL_F32_OUT, rel
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -843,8 +847,8 @@ def test_emu_padded_batch_generate_and_forward_with_images(emu, golden_small):
     """arch.py:227-261 + videollama2_mistral.py:63-108 on the HIP host path: a RIGHT-PADDED batch of two video prompts of
     different lengths through `generate(inputs, attention_mask, images=[...])` gives each sequence the tokens it gets alone
     (finished rows padded with pad_token_id), `forward(input_ids, images=)` returns the logits of every position (golden
-    prefill logits of the real reference), and the spliced mask / embeds follow the reference's layout; with the live reference
-    available, its own padded-batch generate is the cross-check."""
+    prefill logits of the real reference), and the spliced mask / embeds follow the reference's layout; the reference's own
+    batch-2 generate on the same images (tests/golden/reference_checks.pt) is the cross-check."""
     from videollama2_amd.model import VideoLLaMA2Hip
     g = golden_small
     cfg = g["cfg"]
@@ -884,15 +888,11 @@ def test_emu_padded_batch_generate_and_forward_with_images(emu, golden_small):
         m.generate(batch, attention_mask=bad, images=images, max_new_tokens=2)
     with pytest.raises(ValueError, match="media input"):
         m.generate(batch, attention_mask=mask, images=images[:1], max_new_tokens=2)
-    from oracle import ref_harness as RH
-    if RH.reference_available():                                              # the reference's own batch-2 generate (equal lengths)
-        model, _ = RH.build_reference_model(cfg)
-        RH.reseed_weights(model, g["seed"])
-        both = torch.stack([idsA, idsA])
-        ref = model.generate(both, attention_mask=torch.ones_like(both), images=images, do_sample=False, max_new_tokens=3, use_cache=True,
-                             pad_token_id=0, eos_token_id=None)
-        ours = m.generate(both, attention_mask=torch.ones_like(both), images=images, max_new_tokens=3, pad_token_id=0)
-        assert ours.tolist() == ref.tolist()
+    # the reference's own batch-2 generate (equal lengths) on these images, minted by oracle/make_golden.py (mint_reference_checks)
+    ref = torch.load(os.path.join(ROOT, "tests", "golden", "reference_checks.pt"), weights_only=False)["v2_batch2_flipped_tokens"]
+    both = torch.stack([idsA, idsA])
+    ours = m.generate(both, attention_mask=torch.ones_like(both), images=images, max_new_tokens=3, pad_token_id=0)
+    assert ours.tolist() == ref
 
 
 @pytest.mark.parametrize("family", ["v2", "v21"])

@@ -1,11 +1,14 @@
-"""Pins the oracle (oracle/vl2_oracle.py): (a) against golden tensors minted from the REAL reference (travels),
-(b) against the reference itself imported in place (only where /root/reference exists)."""
+"""Pins the oracle (oracle/vl2_oracle.py): (a) against golden tensors minted from the REAL reference, (b) against the
+reference's own encode + greedy tokens on unrounded seeded weights (tests/golden/reference_checks.pt, minted from it)."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from oracle import ref_harness as RH
 from oracle import vl2_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_state_dict_names_cover_golden_config(golden_small):
@@ -46,25 +49,26 @@ def test_frame_sample_golden(golden_small):
         assert np.array_equal(O.frame_sample_uniform(d, n), ids.numpy())
 
 
-@pytest.mark.skipif(not RH.reference_available(), reason="reference tree only exists in the build container")
-def test_oracle_matches_live_reference():
+@pytest.fixture(scope="module")
+def reference_checks():
+    """The reference's own outputs for the two checks below (unrounded seeded weights, seeded frames and ids), minted from the live
+    reference by oracle/make_golden.py (mint_reference_checks)."""
+    return torch.load(os.path.join(ROOT, "tests", "golden", "reference_checks.pt"), weights_only=False)
+
+
+def test_oracle_matches_live_reference(reference_checks):
+    r = reference_checks["v2"]
     cfg = O.config_small(4)
-    model, _ = RH.build_reference_model(cfg)
-    RH.reseed_weights(model, 77)
-    sd = O.seeded_state_dict(cfg, 77, round_bf16=False)
-    ref_sd = {k: v for k, v in model.state_dict().items() if torch.is_floating_point(v)}
-    assert set(ref_sd) == set(dict(O.state_dict_names(cfg)))
-    rng = np.random.default_rng(5)
+    sd = O.seeded_state_dict(cfg, r["seed"], round_bf16=False)
+    assert set(r["state_dict_keys"]) == set(dict(O.state_dict_names(cfg)))
+    rng = np.random.default_rng(r["frames_seed"])
     fr = O.normalise_frames_u8(rng.integers(0, 256, (4, 56, 56, 3), dtype=np.uint8))
     with torch.no_grad():
-        a = model.encode_images_or_videos([(fr, "video")])
         b = O.encode_images_or_videos(sd, cfg, [(fr, "video")])
-        assert torch.allclose(a, b, atol=1e-5, rtol=1e-5)
+        assert torch.allclose(r["encode"], b, atol=1e-5, rtol=1e-5)
         ids = torch.tensor([1] + list(rng.integers(3, 512, 5)) + [-201] + list(rng.integers(3, 512, 4)))
-        out = model.generate(ids[None], attention_mask=torch.ones_like(ids)[None], images=[(fr, "video")], do_sample=False,
-                             max_new_tokens=5, use_cache=True, pad_token_id=0, eos_token_id=None)
         toks, _ = O.generate(sd, cfg, ids, fr, 5)
-        assert out[0].tolist() == toks
+        assert r["tokens"] == toks
 
 
 # ---------------------------------------------------------------- VideoLLaMA2.1 family (SURVEY 8f row 1)
@@ -94,22 +98,16 @@ def test_oracle_v21_matches_reference_goldens(golden_small_v21):
     assert O.n_visual_tokens(16, 27, padding=0) == 1352          # SURVEY 8f row 1 [probe]
 
 
-@pytest.mark.skipif(not RH.reference_available(), reason="reference tree only exists in the build container")
-def test_oracle_v21_matches_live_reference():
+def test_oracle_v21_matches_live_reference(reference_checks):
+    r = reference_checks["v21"]
     cfg = O.config_small_v21(4)
-    model, _ = RH.build_reference_model(cfg)
-    RH.reseed_weights(model, 78)
-    sd = O.seeded_state_dict(cfg, 78, round_bf16=False)
-    ref_sd = {k: v for k, v in model.state_dict().items() if torch.is_floating_point(v)}
-    assert set(ref_sd) == set(dict(O.state_dict_names(cfg)))
-    rng = np.random.default_rng(6)
+    sd = O.seeded_state_dict(cfg, r["seed"], round_bf16=False)
+    assert set(r["state_dict_keys"]) == set(dict(O.state_dict_names(cfg)))
+    rng = np.random.default_rng(r["frames_seed"])
     fr = O.normalise_frames_u8_siglip(rng.integers(0, 256, (4, 56, 56, 3), dtype=np.uint8))
     with torch.no_grad():
-        a = model.encode_images_or_videos([(fr, "video")])
         b = O.encode_images_or_videos(sd, cfg, [(fr, "video")])
-        assert torch.allclose(a, b, atol=1e-5, rtol=1e-5)
+        assert torch.allclose(r["encode"], b, atol=1e-5, rtol=1e-5)
         ids = torch.tensor([1] + list(rng.integers(3, 512, 5)) + [-201] + list(rng.integers(3, 512, 4)))
-        out = model.generate(ids[None], attention_mask=torch.ones_like(ids)[None], images=[(fr, "video")], do_sample=False,
-                             max_new_tokens=5, use_cache=True, pad_token_id=0, eos_token_id=None)
         toks, _ = O.generate(sd, cfg, ids, fr, 5)
-        assert out[0].tolist() == toks
+        assert r["tokens"] == toks

@@ -63,9 +63,11 @@ def _run(targets, verbose=False):
             print(se)
 
 
-def build(force=False, verbose=False):
-    """Builds libvl2hip.so (bf16 elements) and libvl2hip_f16.so (fp16 elements) side by side (two hipcc processes)."""
-    _run([(out, extra) for out, extra in ((OUT, []), (OUT_F16, ["-DVL2_ELEM_F16"])) if force or _stale(out, extra)], verbose)
+def build(force=False, verbose=False, lab=False):
+    """Builds libvl2hip.so (bf16 elements) and libvl2hip_f16.so (fp16 elements) side by side (two hipcc processes); lab=True builds
+    libvl2hip_lab.so beside them as a third."""
+    targets = [(OUT, []), (OUT_F16, ["-DVL2_ELEM_F16"])] + ([(OUT_LAB, ["-DVL2_LAB"])] if lab else [])
+    _run([(out, extra) for out, extra in targets if force or _stale(out, extra)], verbose)
     return OUT
 
 
