@@ -431,6 +431,39 @@ int32_t vl2_llm_prefill(const vl2_llm_desc* w, const void* x, int32_t S, float* 
 int32_t vl2_llm_decode_step(const vl2_llm_desc* w, float* logits, int32_t* tok, int32_t* state, int32_t* hist, float* partial,
                             void* ws, int64_t ws_bytes, void* stream);
 
+
+/* ---- sparse mixture-of-experts block (Mixtral-8x7B, HF:models/mixtral/modeling_mixtral.py MixtralSparseMoeBlock; the reference's
+ * videollama2/model/videollama2_mixtral.py decoder).  Operator by operator (the stage calls above stay dense-only).  Every table lives on
+ * the device: no count reaches the host, so a MoE layer captures into a graph.  E <= 64 experts, 1 <= k <= min(E, 4) per token.
+ * The post-attention RMSNorm weight is folded into the router rows (fp32: W * g, exact) and into every expert's gate/up rows (16-bit,
+ * like vl2_pack_fold_norm); the norms below then use a unit weight.
+ * Row tile of the grouped GEMM: 128.  P = rows of the permuted buffers: a multiple of 128, >= S*k + E*127 (the worst-case padding). */
+/* Route S tokens: x [S, ldx] 16-bit, wr [E, D] fp32 -> ids / wts [S, k] (top-k of softmax(rstd * x wr^T), ties to the lower expert, weights
+ * renormalised over the k), rstd [S] fp32 (scratch: the token's 1/rms), logits [S, E] fp32 or NULL, counts [E], offs [E+1] (expert row
+ * offsets, each padded to 128), gather [P] (permuted row -> token, -1 = padding), inv [S, k] ((token, slot) -> permuted row).  Inside an
+ * expert the rows are in ascending token order.  xg [P, D] / rn_g [P, 2] (or NULL): the permuted rows and their (0, rstd). */
+int32_t vl2_moe_route(const void* x, int32_t ldx, const float* wr, int32_t S, int32_t D, int32_t E, int32_t k, float eps,
+                      int32_t* ids, float* wts, float* rstd, float* logits, int32_t* counts, int32_t* offs, int32_t* gather,
+                      int32_t* inv, int32_t P, void* xg, float* rn_g, void* stream);
+/* Grouped GEMM, ONE launch for all experts: C[p] = epilogue(Norm(A[p]) W_e^T) for the permuted rows p of expert e (offs / counts from
+ * vl2_moe_route, read on the device), W_e = W + e * w_stride ([N, ldw] each).  flags VL2_GEMM_SWIGLU: W_e packed like vl2_pack_gate_up,
+ * C [P, N/2] = silu(gate) * up; row_norm [P, 2] (or NULL) applies the RMSNorm of the rows.  Rows of padding are not written. */
+int32_t vl2_moe_gemm(const void* A, int32_t lda, const void* W, int64_t w_stride, int32_t ldw, void* C, int32_t ldc, const float* row_norm,
+                     float eps, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t P, int32_t N, int32_t K,
+                     int32_t flags, void* stream);
+/* out[t] = x1[t] + sum_j wts[t, j] * y[inv[t, j]] (fp32 in slot order, rounded once; out may be x1); row_norm [S, 2] (or NULL) gets
+ * (0, rstd) of the stored rows for the next norm-carrying GEMM. */
+int32_t vl2_moe_combine(const void* x1, int32_t ldx1, const void* y, int32_t ldy, const int32_t* inv, const float* wts, int32_t S, int32_t k,
+                        int32_t D, float eps, void* out, int32_t ldo, float* row_norm, void* stream);
+/* Decode router: one token x [D] -> ids [k], wts [k] (and logits [E] fp32 or NULL); RMSNorm in the prologue. */
+int32_t vl2_moe_route_gemv(const void* x, const float* wr, int32_t D, int32_t E, int32_t k, float eps, int32_t* ids, float* wts, float* logits,
+                           void* stream);
+/* Decode expert GEMVs over the k experts in ids [k] (device memory: graph-replayable), W_e = W + ids[j] * w_stride ([N, ldw]).
+ * flags VL2_GEMM_SWIGLU: x [K] (RMS-normalised in the prologue), y [k, N/2] = silu(gate) * up per slot (wts / res must be NULL).
+ * flags 0: x = the SwiGLU rows [k, K], y [N] = res + sum_j wts[j] * W_{ids[j]} x[j] (fp32, slot order; res may be NULL). */
+int32_t vl2_moe_gemv(const void* W, int64_t w_stride, int32_t ldw, const void* x, const int32_t* ids, const float* wts, const void* res,
+                     void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

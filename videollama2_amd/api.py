@@ -61,14 +61,21 @@ def config_from_checkpoint(model_path):
     """config.json of a VideoLLaMA2 checkpoint (keys of videollama2_arch.py:49-68 + the HF Mistral / Qwen2 config) -> cfg dict."""
     hf = json.load(open(os.path.join(model_path, "config.json")))
     mtype = hf.get("model_type", "videollama2_mistral")
-    if mtype not in ("videollama2_mistral", "videollama2_qwen2"):
-        raise ValueError(f"HIP path: model type {mtype} not built (videollama2_mistral, videollama2_qwen2)")
+    # videollama2_mixtral: built when the config states its expert counts (every config `save_pretrained` writes carries both: they are
+    # not PretrainedConfig defaults); without them the MoE shape is unknown
+    moe = mtype == "videollama2_mixtral" and "num_local_experts" in hf and "num_experts_per_tok" in hf
+    if mtype not in ("videollama2_mistral", "videollama2_qwen2") and not moe:
+        raise ValueError(f"HIP path: model type {mtype} not built (videollama2_mistral, videollama2_qwen2, videollama2_mixtral with its expert counts)")
     rope = hf.get("rope_theta") or (hf.get("rope_parameters") or {}).get("rope_theta") or 1e6
     l = dict(family="qwen2" if "qwen2" in mtype else "mistral", hidden_size=hf["hidden_size"], intermediate_size=hf["intermediate_size"],
              num_hidden_layers=hf["num_hidden_layers"], num_attention_heads=hf["num_attention_heads"],
              num_key_value_heads=hf.get("num_key_value_heads", hf["num_attention_heads"]),
              head_dim=hf.get("head_dim") or hf["hidden_size"] // hf["num_attention_heads"], vocab_size=hf["vocab_size"],
              rms_norm_eps=hf.get("rms_norm_eps", 1e-5), rope_theta=float(rope))
+    if moe:
+        l.update(family="mixtral", num_local_experts=int(hf["num_local_experts"]), num_experts_per_tok=int(hf["num_experts_per_tok"]))
+        if hf.get("sliding_window") is not None:
+            l.update(sliding_window=hf["sliding_window"], max_position_embeddings=hf.get("max_position_embeddings", 32768))
     cfg = dict(vision=_vision_config(hf, model_path), llm=l, projector=hf.get("mm_projector_type", "stc_connector"),
                num_frames=hf.get("num_frames", NUM_FRAMES))
     return cfg, hf

@@ -35,6 +35,26 @@ def videollama2_72b(num_frames=16):
         projector="stc_connector", num_frames=num_frames)
 
 
+def videollama2_8x7b(num_frames=8):
+    """VideoLLaMA2-8x7B(-Base): CLIP-ViT-L/14-336 + stc_connector + Mixtral-8x7B-Instruct-v0.1 (README.md:121-122 of the reference;
+    videollama2/model/videollama2_mixtral.py): the Mistral-7B attention with every MLP replaced by a sparse MoE block of 8 experts,
+    2 active per token (46.7 B parameters, 93 GB of bf16)."""
+    return dict(
+        vision=dict(family="clip", hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
+                    image_size=336, patch_size=14, layer_norm_eps=1e-5, select_layer=-2),
+        llm=dict(family="mixtral", hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
+                 num_key_value_heads=8, head_dim=128, vocab_size=32000, rms_norm_eps=1e-5, rope_theta=1e6,
+                 num_local_experts=8, num_experts_per_tok=2),
+        projector="stc_connector", num_frames=num_frames)
+
+
+MOE_MAX_EXPERTS, MOE_MAX_TOP_K = 64, 4      # csrc/k_moe.h MOE_MAX_E / MOE_MAX_K (run-time arguments of the MoE kernels up to these)
+
+
+def is_moe(cfg):
+    return cfg["llm"].get("family") == "mixtral"
+
+
 def from_hf_config(hf_cfg, vision_cfg):
     """Build the dict from a Videollama2MistralConfig + CLIPVisionConfig (videollama2_arch.py:49-68 keys)."""
     g = lambda o, k, d=None: getattr(o, k, d)
@@ -77,6 +97,16 @@ def check_supported(cfg):
     for name, n in dims:
         if n % 128:
             errs.append(f"{name} {n} % 128 != 0")
+    if l.get("family") == "mixtral":
+        E, k = l.get("num_local_experts"), l.get("num_experts_per_tok")
+        if E is None or k is None:
+            errs.append("mixtral config without num_local_experts / num_experts_per_tok")
+        elif not (1 <= E <= MOE_MAX_EXPERTS and 1 <= k <= min(E, MOE_MAX_TOP_K)):
+            errs.append(f"MoE with {E} experts, top-{k}: the kernels take E <= {MOE_MAX_EXPERTS} and 1 <= k <= min(E, {MOE_MAX_TOP_K})")
+        sw, mpe = l.get("sliding_window"), l.get("max_position_embeddings")
+        if sw is not None and (mpe is None or sw < mpe):
+            errs.append(f"mixtral sliding_window {sw} < max_position_embeddings {mpe}: a window shorter than the context is not built "
+                        "(the released config has none; compared with the checkpoint's context, not the KV cache the model is built with)")
     if l["hidden_size"] > 8192 or v["hidden_size"] > 8192:
         errs.append("hidden size > 8192 (row-norm / depthwise kernels)")
     if errs:

@@ -79,8 +79,9 @@ struct GemvArgs {
 };
 
 // grid = ceil(N_out / (4*RPW)), block 256; dynamic LDS = K * 2 bytes (x as bf16)
+// (the body takes the workgroup index so that k_moe.h can run it on an expert's rows chosen on the device)
 template <bool SWIGLU, bool OUT_F32, int RPW>
-__global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
+__device__ __forceinline__ void gemv_bf16_body(const GemvArgs& p, int bid) {
     // The fused RMSNorm must give the SAME bits here and in gemv_mr_bf16_kernel (a row of a batched decode step == the
     // single-sequence step): under -ffast-math the two instantiations were free to associate "v * rstd * w" and the
     // sum of squares differently (seen on hardware: one logit row in thousands off by 3e-4).  Fixed order, explicit FMAs.
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
             }
         }
     };
-    const int jfirst = (blockIdx.x * 4 + wave) * RPW;
+    const int jfirst = (bid * 4 + wave) * RPW;
     if (one_pass && jfirst < n_out) issue_row(jfirst, 0);
     // stage x (optionally RMS-normalised: HF MistralRMSNorm, fp32 statistics, result rounded to bf16)
     float rstd = 1.f;
@@ -172,6 +173,11 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
             else ((bf16_t*)p.y)[j] = f2bf(o);
         }
     }
+}
+
+template <bool SWIGLU, bool OUT_F32, int RPW>
+__global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
+    gemv_bf16_body<SWIGLU, OUT_F32, RPW>(p, blockIdx.x);
 }
 
 // gemv_bf16_kernel with the activation vector requested BEFORE the weight row: a wave's loads return in order, so x queued behind the row's

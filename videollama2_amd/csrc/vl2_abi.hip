@@ -32,6 +32,7 @@ static constexpr bool kLab = false;
 #include "k_skinny.h"
 #include "k_stc.h"
 #include "k_vit.h"
+#include "k_moe.h"
 
 static thread_local char g_err[512] = "";
 static int32_t fail(int32_t code, const char* fmt, ...) {
@@ -1404,6 +1405,105 @@ extern "C" int32_t vl2_embed_rows(const int32_t* ids, const void* table, void* o
     if (!ids || !table || !out || n <= 0 || D % 8 || ldo % 8) return fail(VL2_E_BADARG, "vl2_embed_rows: bad args");
     hipLaunchKernelGGL(embed_rows_kernel, dim3(n), dim3(128), 0, ST(stream), ids, (const bf16_t*)table, (bf16_t*)out, D, ldo);
     return launched("vl2_embed_rows");
+}
+
+// ------------------------------------------------------------------------------------------------ sparse MoE (Mixtral), k_moe.h
+static bool moe_rows_ok(int S, int k, int E, int P) {
+    return P % MOE_BM == 0 && (int64_t)P >= (int64_t)S * k + (int64_t)E * (MOE_BM - 1);
+}
+extern "C" int32_t vl2_moe_route(const void* x, int32_t ldx, const float* wr, int32_t S, int32_t D, int32_t E, int32_t k, float eps,
+                                 int32_t* ids, float* wts, float* rstd, float* logits, int32_t* counts, int32_t* offs, int32_t* gather,
+                                 int32_t* inv, int32_t P, void* xg, float* rn_g, void* stream) {
+    if (!x || !wr || !ids || !wts || !rstd || !counts || !offs || !gather || !inv || S <= 0 || D <= 0 || E <= 0 || k <= 0)
+        return fail(VL2_E_BADARG, "vl2_moe_route: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_route: need E <= %d and 1 <= k <= min(E, %d) (E=%d k=%d)", MOE_MAX_E, MOE_MAX_K, E, k);
+    if ((int64_t)S * k > MOE_SCAN_MAX) return fail(VL2_E_UNSUPP, "vl2_moe_route: S * k <= %d (S=%d k=%d)", MOE_SCAN_MAX, S, k);
+    if (D % 8 || ldx % 8 || ldx < D || !ALIGNED16(x) || !ALIGNED16(wr) || (xg && !ALIGNED16(xg)))
+        return fail(VL2_E_SHAPE, "vl2_moe_route: need D%%8==0, ldx>=D and 16-byte aligned rows (D=%d ldx=%d)", D, ldx);
+    if (!moe_rows_ok(S, k, E, P)) return fail(VL2_E_SHAPE, "vl2_moe_route: P=%d must be a multiple of %d and >= S*k + E*%d", P, MOE_BM, MOE_BM - 1);
+    if (xg && !rn_g) return fail(VL2_E_BADARG, "vl2_moe_route: the gathered rows need their row-norm table rn_g");
+    hipStream_t s = ST(stream);
+    hipLaunchKernelGGL(moe_router_kernel, dim3((S + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, ldx, wr, S, D, E, k, eps, ids, wts, rstd, logits);
+    hipLaunchKernelGGL(moe_scan_kernel, dim3(1), dim3(1024), 0, s, (const int*)ids, S, E, k, MOE_BM, P, counts, offs, gather, inv);
+    if (xg) hipLaunchKernelGGL(moe_gather_kernel, dim3(P), dim3(256), 0, s, (const bf16_t*)x, ldx, (const int*)gather, (const float*)rstd, D, (bf16_t*)xg, rn_g);
+    return launched("vl2_moe_route");
+}
+extern "C" int32_t vl2_moe_gemm(const void* A, int32_t lda, const void* W, int64_t w_stride, int32_t ldw, void* C, int32_t ldc, const float* row_norm,
+                                float eps, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t P, int32_t N, int32_t K,
+                                int32_t flags, void* stream) {
+    if (!A || !W || !C || !counts || !offs || S <= 0 || k <= 0 || E <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemm: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemm: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (N % GEMM_BN || K % 64 || lda % 8 || ldw % 8 || ldc % 8 || w_stride % 8 || lda < K || ldw < K || w_stride < (int64_t)N * ldw ||
+        !ALIGNED16(A) || !ALIGNED16(W) || !ALIGNED16(C) || (row_norm && (((uintptr_t)row_norm) & 7)))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm: need N%%%d==0, K%%64==0, 16-byte aligned rows, w_stride >= N*ldw (N=%d K=%d)", GEMM_BN, N, K);
+    if (!moe_rows_ok(S, k, E, P)) return fail(VL2_E_SHAPE, "vl2_moe_gemm: P=%d must be a multiple of %d and >= S*k + E*%d", P, MOE_BM, MOE_BM - 1);
+    if ((int64_t)(GEMM_BM - 1) * lda + K >= ((int64_t)1 << 30) || (int64_t)(GEMM_BN - 1) * ldw + K >= ((int64_t)1 << 30))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm: a tile's rows exceed the kernels' 32-bit buffer offsets");
+    const bool sw = flags & VL2_GEMM_SWIGLU;
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemm: flags other than VL2_GEMM_SWIGLU not built");
+    if (sw && N % 64) return fail(VL2_E_SHAPE, "vl2_moe_gemm: SWIGLU needs N%%64==0");
+    MoeGemmArgs q{};
+    GemmArgs& a = q.g;
+    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = C;
+    a.M = P; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc;
+    a.stats_out_np = N / 64; a.stats_in_np = K / 64; a.idx_ld = P;
+    if (row_norm) { a.norm = VL2_NORM_RMS; a.norm_eps = eps; a.row_norm = row_norm; }
+    q.offs = offs; q.counts = counts; q.w_stride = w_stride; q.E = E; q.rt_cap = P / MOE_BM;
+    const dim3 grid((unsigned)(q.rt_cap * (N / GEMM_BN)));
+    hipStream_t s = ST(stream);
+    if (sw) {
+        lds_attr<moe_gemm_kernel<true>>(GEMML_LDS_BYTES);
+        hipLaunchKernelGGL((moe_gemm_kernel<true>), grid, dim3(512), GEMML_LDS_BYTES, s, q);
+    } else {
+        lds_attr<moe_gemm_kernel<false>>(GEMML_LDS_BYTES);
+        hipLaunchKernelGGL((moe_gemm_kernel<false>), grid, dim3(512), GEMML_LDS_BYTES, s, q);
+    }
+    return launched("vl2_moe_gemm");
+}
+extern "C" int32_t vl2_moe_combine(const void* x1, int32_t ldx1, const void* y, int32_t ldy, const int32_t* inv, const float* wts, int32_t S, int32_t k,
+                                   int32_t D, float eps, void* out, int32_t ldo, float* row_norm, void* stream) {
+    if (!x1 || !y || !inv || !wts || !out || S <= 0 || k <= 0 || D <= 0) return fail(VL2_E_BADARG, "vl2_moe_combine: null pointer or empty shape");
+    if (k > MOE_MAX_K) return fail(VL2_E_UNSUPP, "vl2_moe_combine: k <= %d", MOE_MAX_K);
+    if (D % 8 || ldx1 % 8 || ldy % 8 || ldo % 8 || ldx1 < D || ldy < D || ldo < D || !ALIGNED16(x1) || !ALIGNED16(y) || !ALIGNED16(out) ||
+        (row_norm && (((uintptr_t)row_norm) & 7)))
+        return fail(VL2_E_SHAPE, "vl2_moe_combine: need D%%8==0, ldx1 / ldy / ldo >= D and 16-byte aligned rows (D=%d)", D);
+    hipLaunchKernelGGL(moe_combine_kernel, dim3(S), dim3(256), 0, ST(stream), (const bf16_t*)x1, ldx1, (const bf16_t*)y, ldy, (const int*)inv, wts, k, D, eps,
+                       (bf16_t*)out, ldo, row_norm);
+    return launched("vl2_moe_combine");
+}
+extern "C" int32_t vl2_moe_route_gemv(const void* x, const float* wr, int32_t D, int32_t E, int32_t k, float eps, int32_t* ids, float* wts, float* logits,
+                                      void* stream) {
+    if (!x || !wr || !ids || !wts || D <= 0 || E <= 0 || k <= 0) return fail(VL2_E_BADARG, "vl2_moe_route_gemv: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_route_gemv: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (D % 8 || !ALIGNED16(x) || !ALIGNED16(wr)) return fail(VL2_E_SHAPE, "vl2_moe_route_gemv: need D%%8==0 and 16-byte aligned rows");
+    hipLaunchKernelGGL(moe_router_kernel, dim3(1), dim3(256), 0, ST(stream), (const bf16_t*)x, D, wr, 1, D, E, k, eps, ids, wts,
+                       (float*)nullptr, logits);
+    return launched("vl2_moe_route_gemv");
+}
+extern "C" int32_t vl2_moe_gemv(const void* W, int64_t w_stride, int32_t ldw, const void* x, const int32_t* ids, const float* wts, const void* res,
+                                void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream) {
+    if (!W || !x || !ids || !y || E <= 0 || k <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemv: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemv: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (K % 8 || ldw % 8 || ldw < K || w_stride < (int64_t)N * ldw || !ALIGNED16(W) || !ALIGNED16(x) || !ALIGNED16(y))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemv: need K%%8==0, 16-byte aligned rows, w_stride >= N*ldw");
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemv: flags other than VL2_GEMM_SWIGLU not built");
+    hipStream_t s = ST(stream);
+    if (flags & VL2_GEMM_SWIGLU) {
+        if (N % 64 || K > 32704 || wts || res) return fail(VL2_E_SHAPE, "vl2_moe_gemv: SWIGLU needs N%%64==0, K<=32704 and no wts / res");
+        GemvArgs a{(const bf16_t*)W, (const bf16_t*)x, nullptr, nullptr, y, N, K, ldw, eps, nullptr, 0, 0, 0, 1};
+        hipLaunchKernelGGL(moe_gemv_gu_kernel, dim3((N / 2 + 3) / 4, k), dim3(256), (size_t)K * 2, s, a, (const int*)ids, (long long)w_stride, N / 2);
+        return launched("vl2_moe_gemv");
+    }
+    if (!wts) return fail(VL2_E_BADARG, "vl2_moe_gemv: the down form needs the routing weights");
+    const size_t lds = (size_t)k * K * 2;
+    if (lds > 160 * 1024) return fail(VL2_E_SHAPE, "vl2_moe_gemv: k * K * 2 bytes of activations must fit the LDS (k=%d K=%d)", k, K);
+    const dim3 g((N + 3) / 4), b(256);
+#define VL2_MOE_DOWN(KS) do { lds_attr<moe_gemv_down_kernel<KS>>(160 * 1024); \
+        hipLaunchKernelGGL((moe_gemv_down_kernel<KS>), g, b, lds, s, (const bf16_t*)W, (long long)w_stride, ldw, (const bf16_t*)x, (const int*)ids, wts, \
+                           (const bf16_t*)res, (bf16_t*)y, N, K); } while (0)
+    if (k == 1) VL2_MOE_DOWN(1); else if (k == 2) VL2_MOE_DOWN(2); else if (k == 3) VL2_MOE_DOWN(3); else VL2_MOE_DOWN(4);
+#undef VL2_MOE_DOWN
+    return launched("vl2_moe_gemv");
 }
 
 #include "vl2_stage.inc"

@@ -193,9 +193,7 @@ class HipMistralDecoder(nn.Module):
             ops.rope_kv(qkv, q, kcache[li], vcache[li], self.cos_t, self.sin_t, nh, nkv, 0)
             ops.attn_fwd(q, kcache[li], vcache[li], o, (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
                          (0, hd, nh * hd), 1, nh, S, S, nh // nkv, hd ** -0.5, True, 0, hd)
-            x = self._row_parallel(o, lw["wo"], x, rs, rn)
-            a = ops.gemm(x, lw["wgu"], swiglu=True, norm=(ops.NORM_RMS, rn, self.eps, None), mfma16=True)
-            x = self._row_parallel(a, lw["wd"], x, rs, rn)
+            x = self._prefill_block_out(lw, o, x, rs, rn)
         self.pos = S
         self.last_hidden = x
         if return_all_logits:
@@ -203,6 +201,13 @@ class HipMistralDecoder(nn.Module):
             return ops.gemm(h, self.w["lm_head"], out_f32=True)
         return ops.gemv(self.w["lm_head"], x[S - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True,
                         out=self.logits if logits_out is None else logits_out)
+
+    def _prefill_block_out(self, lw, o, x, rs, rn):
+        """The rest of a prefill layer after attention: x + o_proj(o), then the MLP (SwiGLU) with its residual; leaves (0, rstd) of
+        the result in `rn` for the next layer's q/k/v GEMM.  (HipMixtralDecoder replaces the MLP by its sparse MoE block.)"""
+        x = self._row_parallel(o, lw["wo"], x, rs, rn)
+        a = ops.gemm(x, lw["wgu"], swiglu=True, norm=(ops.NORM_RMS, rn, self.eps, None), mfma16=True)
+        return self._row_parallel(a, lw["wd"], x, rs, rn)
 
     # ------------------------------------------------------------------ decode (M = 1, HBM-bound GEMVs)
     def _decode_kernels(self, dyn):
@@ -227,11 +232,17 @@ class HipMistralDecoder(nn.Module):
             ops.gemv(lw["wqkv"], x, norm_w=self.w["ones"], eps=self.eps, out=b["qkv"], bias=lw["bqkv"])   # ln weight folded into wqkv
             ops.attn_decode(b["qkv"], self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, self.partial, b["o"], nh, nkv,
                             self.pos, hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
-            r0 = self.tp_rank == 0                                              # the residual rides on rank 0's partial sum
-            self._reduce(ops.gemv(lw["wo"], b["o"], res=x if r0 else None, out=b["x1"]))          # x1 = x + attn
-            ops.gemv(lw["wgu"], b["x1"], norm_w=self.w["ones"], eps=self.eps, swiglu=True, out=b["a"])
-            self._reduce(ops.gemv(lw["wd"], b["a"], res=b["x1"] if r0 else None, out=x))          # x = x1 + mlp (x's old value is dead)
+            self._decode_block_out(lw, x)
         ops.gemv(self.w["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=self.logits)
+
+    def _decode_block_out(self, lw, x):
+        """The rest of a decode layer after attention (o in self._b["o"]): x1 = x + o_proj(o), then x = x1 + MLP(x1) in place.
+        (HipMixtralDecoder replaces the MLP by its sparse MoE GEMVs.)"""
+        b = self._b
+        r0 = self.tp_rank == 0                                              # the residual rides on rank 0's partial sum
+        self._reduce(ops.gemv(lw["wo"], b["o"], res=x if r0 else None, out=b["x1"]))          # x1 = x + attn
+        ops.gemv(lw["wgu"], b["x1"], norm_w=self.w["ones"], eps=self.eps, swiglu=True, out=b["a"])
+        self._reduce(ops.gemv(lw["wd"], b["a"], res=b["x1"] if r0 else None, out=x))          # x = x1 + mlp (x's old value is dead)
 
     @torch.no_grad()
     def decode_step(self, tok_dev=None):
@@ -588,3 +599,75 @@ class HipMistralDecoder(nn.Module):
 
 
 HipQwen2Decoder = HipMistralDecoder      # same decoder; the q/k/v bias is picked up from the state dict (weights.pack_decoder)
+
+
+class HipMixtralDecoder(HipMistralDecoder):
+    """The decoder of VideoLLaMA2-8x7B (videollama2/model/videollama2_mixtral.py, HF:models/mixtral/modeling_mixtral.py): the Mistral
+    attention, RoPE, norms and lm_head of the parent, and in every layer a sparse MoE block (MixtralSparseMoeBlock) in place of the MLP --
+    router, token grouping, grouped expert GEMMs and combine on csrc/k_moe.h.  Runs operator by operator (the stage calls are
+    dense-only); every routing table stays on the device, so the prefill and the decode step both capture into graphs.
+    Single GPU, batch 1, 16-bit weights: tensor parallelism, fp8 weights and batched / continuous decoding raise NotImplementedError."""
+
+    def __init__(self, cfg, state_dict, device="cuda", max_seq_len=4096, n_layers=None, tp_group=None, tp_shard=None, tp_local=None):
+        if tp_group is not None or tp_shard is not None or tp_local is not None:
+            raise NotImplementedError("MoE (mixtral) decoder: tensor / expert parallelism not built")
+        super().__init__(cfg, state_dict, device, max_seq_len, n_layers)
+        l = cfg["llm"]
+        self.E, self.k, self.I = l["num_local_experts"], l["num_experts_per_tok"], l["intermediate_size"]
+        self.moe_ids = torch.zeros((self.k,), dtype=torch.int32, device=self._dev)
+        self.moe_wts = torch.zeros((self.k,), dtype=torch.float32, device=self._dev)
+        self._b["a"] = torch.empty((self.k, self.I), dtype=_lib.elem_dtype(), device=self._dev)
+
+    def _use_stage(self, cache=None):
+        return False
+
+    def enable_fp8_decode(self, on=True):
+        raise NotImplementedError("MoE (mixtral) decoder: fp8 weights not built")
+
+    def enable_fp8_prefill(self, on=True):
+        raise NotImplementedError("MoE (mixtral) decoder: fp8 weights not built")
+
+    def prefill_batch(self, xs, caches, logits_out):
+        raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")
+
+    def generate_batch(self, *args, **kwargs):
+        raise NotImplementedError("MoE (mixtral) decoder: batched decoding not built")
+
+    def _ensure_batch(self, B, owner=None):
+        raise NotImplementedError("MoE (mixtral) decoder: batched / continuous decoding not built")
+
+    def moe_block(self, lw, x1, rn):
+        """x1 [S, D] (attention output + residual) -> x1 + MoE(RMSNorm(x1)); rn [S, 2] gets (0, rstd) of the result for the next
+        layer's norm-carrying q/k/v GEMM.  Route (ids, weights, counts, offsets, gather / inverse tables, permuted rows), grouped
+        gate/up + SwiGLU, grouped down, combine: five launches' worth of kernels, no host synchronisation."""
+        S = x1.shape[0]
+        r = ops.moe_route(x1, lw["wr"], self.k, self.eps)
+        self.last_route = r                                   # (the tables of the last layer routed: tests follow the kernel's choice)
+        a = ops.moe_gemm(r["xg"], lw["wgu"], r, S, self.k, swiglu=True, row_norm=r["rn"], eps=self.eps)
+        y = ops.moe_gemm(a, lw["wd"], r, S, self.k)
+        return ops.moe_combine(x1, y, r, self.eps, out=x1, row_norm=rn)
+
+    @torch.no_grad()
+    def prefill(self, x, return_all_logits=False, cache=None, logits_out=None):
+        if cache is not None:
+            raise NotImplementedError("MoE (mixtral) decoder: external caches (batched decoding) not built")
+        return super().prefill(x, return_all_logits=return_all_logits, logits_out=logits_out)
+
+    def _prefill_block_out(self, lw, o, x, rs, rn):
+        """x1 = x + o_proj(o) (its norm is taken by the router), then the sparse MoE block; the combine leaves (0, rstd) in `rn`."""
+        return self.moe_block(lw, ops.gemm(o, lw["wo"], res=x), rn)
+
+    def _decode_block_out(self, lw, x):
+        """x1 = x + o_proj(o); router GEMV (+RMSNorm, softmax, top-k -> ids / weights on the device); gate/up+SwiGLU GEMV of the k chosen
+        experts (one launch); down GEMV of both (one launch, weighted, + residual) into x.  No host read: the step replays as a graph."""
+        b = self._b
+        ops.gemv(lw["wo"], b["o"], res=x, out=b["x1"])
+        ops.moe_route_gemv(b["x1"], lw["wr"], self.moe_ids, self.moe_wts, self.eps)
+        ops.moe_gemv(lw["wgu"], b["x1"], self.moe_ids, swiglu=True, eps=self.eps, out=b["a"])
+        ops.moe_gemv(lw["wd"], b["a"], self.moe_ids, wts=self.moe_wts, res=b["x1"], out=x)
+
+
+def make_decoder(cfg, *args, **kwargs):
+    """The decoder class of the config's family: Mistral / Qwen2 (dense) or Mixtral (sparse MoE)."""
+    cls = HipMixtralDecoder if cfg["llm"].get("family") == "mixtral" else HipMistralDecoder
+    return cls(cfg, *args, **kwargs)

@@ -13,7 +13,7 @@ from . import _lib, ops
 from .config import check_supported
 from .connector import HipSTCConnector
 from .constants import MODAL_INDEX_MAP, NUM_FRAMES
-from .decoder import HipMistralDecoder
+from .decoder import HipMistralDecoder, make_decoder
 from .dist import FrameSharder
 from .tower import HipCLIPVisionTower, HipSiglipVisionTower
 
@@ -32,7 +32,7 @@ class VideoLLaMA2Hip(nn.Module):
         tower_cls = HipSiglipVisionTower if cfg["vision"].get("family", "clip") == "siglip" else HipCLIPVisionTower   # encoder.py:157-160
         self.vision_tower = tower_cls(cfg, state_dict, device, image_processor=image_processor)
         self.mm_projector = HipSTCConnector(state_dict, device, padding=0 if mm_projector_type == "stc_connector_v35" else 1)
-        self.decoder = HipMistralDecoder(cfg, state_dict, device, max_seq_len, n_llm_layers, tp_group=tp_group)
+        self.decoder = make_decoder(cfg, state_dict, device, max_seq_len, n_llm_layers, tp_group=tp_group)   # Mixtral: HipMixtralDecoder
         self.sharder = sharder or FrameSharder()
 
     def get_vision_tower(self):

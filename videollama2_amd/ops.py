@@ -616,3 +616,77 @@ def llm_prefill(desc, x, logits_out, fp8=False):
 def llm_decode_step(desc, logits, tok, state, hist, partial, ws, fp8=False):
     desc.flags = _CTL["stage_flags"] | (STAGE_DECODE_FP8 if fp8 else 0)
     _lib.call("vl2_llm_decode_step", ctypes.byref(desc), _p(logits), _p(tok), _p(state), _p(hist), _p(partial), _p(ws), ws.numel(), _stream())
+
+
+# ------------------------------------------------------------------------------------------------ sparse MoE (Mixtral), csrc/k_moe.h
+MOE_BM = 128           # row tile of the grouped GEMM: every expert's rows are padded to it
+
+
+def moe_rows(S, k, E):
+    """Rows of the permuted buffers for S tokens: the worst case S*k + E*(MOE_BM - 1), rounded up to the row tile (the counts stay on
+    the device, so the buffers are sized without them)."""
+    return (S * k + E * (MOE_BM - 1) + MOE_BM - 1) // MOE_BM * MOE_BM
+
+
+def moe_route(x, wr, k, eps, xg=True, logits=False):
+    """include/vl2hip.h vl2_moe_route: x [S, D], wr [E, D] fp32 (norm folded) -> dict of device tensors: ids / wts [S, k], counts [E],
+    offs [E+1], gather [P], inv [S, k], and (xg=True) the permuted rows xg [P, D] with their row-norm table rn [P, 2]."""
+    _chk(x, _lib.elem_dtype(), "x"); _chk(wr, torch.float32, "wr")
+    S, D = x.shape
+    E = wr.shape[0]
+    P = moe_rows(S, k, E)
+    dev = x.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    r = dict(ids=torch.empty((S, k), **i32), wts=torch.empty((S, k), dtype=torch.float32, device=dev),
+             rstd=torch.empty((S,), dtype=torch.float32, device=dev), counts=torch.empty((E,), **i32), offs=torch.empty((E + 1,), **i32),
+             gather=torch.empty((P,), **i32), inv=torch.empty((S, k), **i32), P=P,
+             logits=torch.empty((S, E), dtype=torch.float32, device=dev) if logits else None,
+             xg=torch.empty((P, D), dtype=_lib.elem_dtype(), device=dev) if xg else None,
+             rn=torch.empty((P, 2), dtype=torch.float32, device=dev) if xg else None)
+    _lib.call("vl2_moe_route", _p(x), x.stride(0), _p(wr), S, D, E, k, float(eps), _p(r["ids"]), _p(r["wts"]), _p(r["rstd"]), _p(r["logits"]),
+              _p(r["counts"]), _p(r["offs"]), _p(r["gather"]), _p(r["inv"]), P, _p(r["xg"]), _p(r["rn"]), _stream())
+    return r
+
+
+def moe_gemm(a, w, route, S, k, swiglu=False, row_norm=None, eps=0.0, out=None):
+    """include/vl2hip.h vl2_moe_gemm: the grouped GEMM over the permuted rows a [P, K] (route = moe_route's dict), w [E, N, K] (SwiGLU:
+    each expert packed like pack_gate_up) -> [P, N] (SwiGLU [P, N/2]); rows of padding are left unwritten."""
+    _chk(a, _lib.elem_dtype(), "a"); _chk(w, _lib.elem_dtype(), "w"); _chk(row_norm, torch.float32, "row_norm")
+    E, N, K = w.shape
+    P = a.shape[0]
+    if out is None:
+        out = torch.empty((P, N // 2 if swiglu else N), dtype=_lib.elem_dtype(), device=a.device)
+    _lib.call("vl2_moe_gemm", _p(a), a.stride(0), _p(w), w.stride(0), w.stride(1), _p(out), out.stride(0), _p(row_norm), float(eps),
+              _p(route["counts"]), _p(route["offs"]), S, k, E, P, N, K, GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
+
+
+def moe_combine(x1, y, route, eps, out=None, row_norm=None):
+    """include/vl2hip.h vl2_moe_combine: x1 [S, D] + sum_j w_tj y[inv(t, j)] -> out (may be x1); row_norm [S, 2] gets (0, rstd)."""
+    _chk(x1, _lib.elem_dtype(), "x1"); _chk(y, _lib.elem_dtype(), "y"); _chk(row_norm, torch.float32, "row_norm")
+    S, D = x1.shape
+    k = route["inv"].shape[1]
+    out = torch.empty_like(x1) if out is None else out
+    _lib.call("vl2_moe_combine", _p(x1), x1.stride(0), _p(y), y.stride(0), _p(route["inv"]), _p(route["wts"]), S, k, D, float(eps),
+              _p(out), out.stride(0), _p(row_norm), _stream())
+    return out
+
+
+def moe_route_gemv(x, wr, ids, wts, eps, logits=None):
+    """include/vl2hip.h vl2_moe_route_gemv: one token x [D] -> ids [k] int32, wts [k] fp32 (device buffers, written in place)."""
+    _chk(x, _lib.elem_dtype(), "x"); _chk(wr, torch.float32, "wr"); _chk(wts, torch.float32, "wts"); _chk(logits, torch.float32, "logits")
+    E, D = wr.shape
+    _lib.call("vl2_moe_route_gemv", _p(x), _p(wr), D, E, ids.numel(), float(eps), _p(ids), _p(wts), _p(logits), _stream())
+
+
+def moe_gemv(w, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
+    """include/vl2hip.h vl2_moe_gemv over the experts in ids [k] (device): swiglu=True: x [D] -> [k, N/2] (RMSNorm with the folded weight);
+    else x = [k, K] SwiGLU rows -> [N] = res + sum_j wts[j] * W_{ids[j]} x[j]."""
+    _chk(w, _lib.elem_dtype(), "w"); _chk(x, _lib.elem_dtype(), "x"); _chk(res, _lib.elem_dtype(), "res"); _chk(wts, torch.float32, "wts")
+    E, N, K = w.shape
+    k = ids.numel()
+    if out is None:
+        out = torch.empty((k, N // 2) if swiglu else (N,), dtype=_lib.elem_dtype(), device=w.device)
+    _lib.call("vl2_moe_gemv", _p(w), w.stride(0), w.stride(1), _p(x), _p(ids), _p(wts), _p(res), _p(out), E, k, N, K, float(eps),
+              GEMM_SWIGLU if swiglu else 0, _stream())
+    return out

@@ -201,6 +201,9 @@ def pack_decoder(sd, cfg, dev, n_layers=None, tp_rank=0, tp_size=1):
         out[:, :i1 - i0] = w
         return out
 
+    moe = l.get("family") == "mixtral"
+    if moe and tp_size > 1:
+        raise NotImplementedError("MoE (mixtral) decoder: tensor / expert parallelism not built")
     out = dict(embed=_bf(sd["model.embed_tokens.weight"], dev), norm_w=_f32(sd["model.norm.weight"], dev),
                lm_head=_bf(sd["lm_head.weight"], dev), layers=[],
                ones=torch.ones((l["hidden_size"],), dtype=torch.float32, device=dev))   # unit RMSNorm weight: the real ones are folded below
@@ -215,11 +218,49 @@ def pack_decoder(sd, cfg, dev, n_layers=None, tp_rank=0, tp_size=1):
         # x with a unit weight in their prologue
         wqkv, _, _ = fold_norm(torch.cat([sd[a + "q_proj.weight"][q0:q1], sd[a + "k_proj.weight"][k0:k1], sd[a + "v_proj.weight"][k0:k1]], 0),
                                sd[p + "input_layernorm.weight"], dev=dev)
+        if moe:
+            out["layers"].append(dict(bqkv=bqkv, wqkv=wqkv, wo=_bf(sd[a + "o_proj.weight"][:, q0:q1], dev),
+                                      **pack_moe_layer(sd, p, l, dev)))
+            continue
         wgu, _, _ = fold_norm(pack_gate_up(rows_padded(sd[p + "mlp.gate_proj.weight"]), rows_padded(sd[p + "mlp.up_proj.weight"])),
                               sd[p + "post_attention_layernorm.weight"], dev=dev)
         out["layers"].append(dict(bqkv=bqkv, wqkv=wqkv, wo=_bf(sd[a + "o_proj.weight"][:, q0:q1], dev), wgu=wgu,
                                   wd=_bf(cols_padded(sd[p + "mlp.down_proj.weight"]), dev)))
     return out
+
+
+def moe_expert_weights(sd, p, E, I, e):
+    """(gate [I, D], up [I, D], down [D, I]) of expert e of layer prefix p (`model.layers.N.`), from either key layout:
+    transformers >= 5 (MixtralExperts: mlp.experts.gate_up_proj [E, 2I, D], gate rows first; mlp.experts.down_proj [E, D, I]) or
+    transformers 4.x, which checkpoints saved before 5.0 carry (block_sparse_moe.experts.{e}.w1 = gate, w3 = up, w2 = down)."""
+    if p + "mlp.experts.gate_up_proj" in sd:
+        gu = sd[p + "mlp.experts.gate_up_proj"][e]
+        return gu[:I], gu[I:], sd[p + "mlp.experts.down_proj"][e]
+    b = f"{p}block_sparse_moe.experts.{e}."
+    return sd[b + "w1.weight"], sd[b + "w3.weight"], sd[b + "w2.weight"]
+
+
+def moe_router_weight(sd, p):
+    return sd[p + "mlp.gate.weight"] if (p + "mlp.gate.weight") in sd else sd[p + "block_sparse_moe.gate.weight"]
+
+
+def pack_moe_layer(sd, p, l, dev):
+    """One Mixtral sparse-MoE block -> csrc/k_moe.h layouts, expert by expert into preallocated device tensors (a 93 GB checkpoint
+    never needs a second full host copy): wr [E, D] fp32 router rows times the post_attention_layernorm weight (exact: a rounded fold
+    would flip close top-k decisions), wgu [E, 2I, D] (every expert's gate/up packed like the dense pack_gate_up, the norm folded in by
+    fold_norm), wd [E, D, I]."""
+    E, D, I = l["num_local_experts"], l["hidden_size"], l["intermediate_size"]
+    g = sd[p + "post_attention_layernorm.weight"]
+    wr = _aligned((_f32(moe_router_weight(sd, p), dev) * _f32(g, dev)[None, :]).contiguous())   # fp32: exact product, no rounding
+    wgu = torch.empty((E, 2 * I, D), dtype=_lib.elem_dtype(), device=dev)
+    wd = torch.empty((E, D, I), dtype=_lib.elem_dtype(), device=dev)
+    v5 = (p + "mlp.experts.gate_up_proj") in sd
+    gu5, dn5 = (sd[p + "mlp.experts.gate_up_proj"], sd[p + "mlp.experts.down_proj"]) if v5 else (None, None)
+    for e in range(E):
+        gate, up, down = (gu5[e, :I], gu5[e, I:], dn5[e]) if v5 else moe_expert_weights(sd, p, E, I, e)
+        wgu[e].copy_(fold_norm(pack_gate_up(gate, up), g, dev=dev)[0])
+        wd[e].copy_(down.detach().to(device=dev, dtype=_lib.elem_dtype()))
+    return dict(wr=wr, wgu=wgu, wd=wd)
 
 
 def state_dict_names(cfg):
@@ -267,10 +308,14 @@ def state_dict_names(cfg):
     for i in range(l["num_hidden_layers"]):
         p = f"model.layers.{i}."
         out += [(p + "self_attn.q_proj.weight", (nh * hd, D)), (p + "self_attn.k_proj.weight", (nkv * hd, D)),
-                (p + "self_attn.v_proj.weight", (nkv * hd, D)), (p + "self_attn.o_proj.weight", (D, nh * hd)),
-                (p + "mlp.gate_proj.weight", (I, D)), (p + "mlp.up_proj.weight", (I, D)),
-                (p + "mlp.down_proj.weight", (D, I)),
-                (p + "input_layernorm.weight", (D,)), (p + "post_attention_layernorm.weight", (D,))]
+                (p + "self_attn.v_proj.weight", (nkv * hd, D)), (p + "self_attn.o_proj.weight", (D, nh * hd))]
+        if l.get("family", "mistral") == "mixtral":           # MixtralSparseMoeBlock, transformers >= 5 naming
+            E = l["num_local_experts"]
+            out += [(p + "mlp.gate.weight", (E, D)), (p + "mlp.experts.gate_up_proj", (E, 2 * I, D)),
+                    (p + "mlp.experts.down_proj", (E, D, I))]
+        else:
+            out += [(p + "mlp.gate_proj.weight", (I, D)), (p + "mlp.up_proj.weight", (I, D)), (p + "mlp.down_proj.weight", (D, I))]
+        out += [(p + "input_layernorm.weight", (D,)), (p + "post_attention_layernorm.weight", (D,))]
         if l.get("family", "mistral") == "qwen2":
             out += [(p + "self_attn.q_proj.bias", (nh * hd,)), (p + "self_attn.k_proj.bias", (nkv * hd,)),
                     (p + "self_attn.v_proj.bias", (nkv * hd,))]
@@ -298,6 +343,8 @@ def random_state_dict(cfg, device, seed=1234, n_llm_layers=None):
             fan_in = 1
             for s in shape[1:]:
                 fan_in *= s
+            if ".mlp.experts." in name:          # [E, N, K] stacked experts: fan-in K
+                fan_in = shape[-1]
             x = x * (fan_in ** -0.5)
         else:
             x = 0.5 * x
@@ -347,6 +394,8 @@ class LazyRandomStateDict:
             fan_in = 1
             for d in shape[1:]:
                 fan_in *= d
+            if ".mlp.experts." in name:          # [E, N, K] stacked experts: fan-in K
+                fan_in = shape[-1]
             x = x * (fan_in ** -0.5)
         else:
             x = 0.5 * x
