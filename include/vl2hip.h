@@ -305,6 +305,14 @@ int32_t vl2_attn_decode(const void* qkv, void* kcache, void* vcache, const float
 int32_t vl2_attn_decode_batched(const void* qkv, void* kcache, void* vcache, const float* cos_t, const float* sin_t, float* partial,
                                 void* out, int32_t B, int64_t qkv_bs, int64_t cache_bs, int64_t out_bs, int32_t nh, int32_t nkv,
                                 int32_t smax, const int32_t* pos_dev, int32_t ctx_cap, float scale, void* stream);
+/* Append attention (k_attn_append.h): n new query rows at positions P .. P+n-1 of ONE sequence against the P + n keys of its cache
+ * (the rows P .. P+n-1 already written, e.g. by vl2_rope_kv with pos0 = P); key j is visible to row i iff j <= P + i.  q: roped rows
+ * [n, q_rs] (q head h at column h*128), caches [nkv, smax, 128], out [n, o_rs] 16-bit.  head_dim 128 only.  Split-KV: fp32 partials of
+ * every (row, key split) go to `ws` and are merged in split order (no atomics: deterministic).  ws_bytes >= vl2_attn_append_ws_bytes. */
+int32_t vl2_attn_append(const void* q, int64_t q_rs, const void* kcache, const void* vcache, void* out, int64_t o_rs, int32_t P, int32_t n,
+                        int32_t nh, int32_t nkv, int32_t smax, float scale, float* ws, int64_t ws_bytes, void* stream);
+/* bytes of the workspace vl2_attn_append needs for (P, n, nh) (an upper bound that does not depend on nkv). */
+int64_t vl2_attn_append_ws_bytes(int32_t P, int32_t n, int32_t nh);
 /* greedy argmax (first maximal index) of fp32 logits -> *tok (device int32) and hist[step] if hist != NULL.
  * state != NULL (device int32[2] = {position, step}): hist index = state[1], then both counters advance by one, so the
  * whole decode step is replayable from a hipGraph.  HF:generation/utils.py _sample with do_sample=False. */

@@ -120,7 +120,11 @@ MOE_SIGNATURES = {
     "vl2_moe_route_gemv": [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
     "vl2_moe_gemv": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
 }
-EXPORTS = ["vl2_version", "vl2_elem_name", "vl2_last_error_string", "vl2_workspace_bytes", "vl2_vit_workspace_bytes", "vl2_stc_workspace_bytes", "vl2_llm_workspace_bytes", "vl2_dwconv_mean_workspace_bytes"] + list(SIGNATURES) + list(MOE_SIGNATURES)
+# the append attention of a prefill on top of a resident KV cache (include/vl2hip.h vl2_attn_append): a table of its own for the same reason
+APPEND_SIGNATURES = {
+    "vl2_attn_append": [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
+}
+EXPORTS = ["vl2_version", "vl2_elem_name", "vl2_last_error_string", "vl2_workspace_bytes", "vl2_vit_workspace_bytes", "vl2_stc_workspace_bytes", "vl2_llm_workspace_bytes", "vl2_dwconv_mean_workspace_bytes", "vl2_attn_append_ws_bytes"] + list(SIGNATURES) + list(MOE_SIGNATURES) + list(APPEND_SIGNATURES)
 
 _lib = None
 # ---- element type of the build in use: "bf16" (libvl2hip.so, the default: BASELINE.json configs[1]) or "fp16" (libvl2hip_f16.so = the same
@@ -218,7 +222,9 @@ def load():
     lib.vl2_dwconv_mean_workspace_bytes.argtypes = [_i32, _i32]
     lib.vl2_llm_workspace_bytes.restype = _i64
     lib.vl2_llm_workspace_bytes.argtypes = [ctypes.POINTER(LlmDesc), _i32]
-    for name, args in list(SIGNATURES.items()) + list(MOE_SIGNATURES.items()):
+    lib.vl2_attn_append_ws_bytes.restype = _i64
+    lib.vl2_attn_append_ws_bytes.argtypes = [_i32, _i32, _i32]
+    for name, args in list(SIGNATURES.items()) + list(MOE_SIGNATURES.items()) + list(APPEND_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = _i32
         fn.argtypes = args

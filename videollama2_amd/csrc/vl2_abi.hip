@@ -33,6 +33,7 @@ static constexpr bool kLab = false;
 #include "k_stc.h"
 #include "k_vit.h"
 #include "k_moe.h"
+#include "k_attn_append.h"
 
 static thread_local char g_err[512] = "";
 static int32_t fail(int32_t code, const char* fmt, ...) {
@@ -1353,6 +1354,44 @@ extern "C" int32_t vl2_attn_decode_batched(const void* qkv, void* kcache, void* 
     hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(nh, B), dim3(128), 0, ST(stream), partial, (bf16_t*)out, nsplit, 0, pos_dev,
                        partial_bs, (long)out_bs);
     return launched("vl2_attn_decode_batched");
+}
+// Split of the keys for vl2_attn_append: enough (kv head, row block, split) workgroups to fill the 256 CUs, at least two 64-key tiles per
+// split (a split's fp32 partials cost about what one tile's loads do), at most APPEND_MAX_SPLITS.
+static void attn_append_split(int P, int n, int group, int nkv, int& chunk, int& nsplit) {
+    const int T = (P + n + 63) / 64, rb = (n * group + 127) / 128;
+    int want = (256 + nkv * rb - 1) / (nkv * rb);
+    want = want < (T + 1) / 2 ? want : (T + 1) / 2;
+    want = want < APPEND_MAX_SPLITS ? want : APPEND_MAX_SPLITS;
+    want = want > 1 ? want : 1;
+    const int tps = (T + want - 1) / want;
+    chunk = tps * 64;
+    nsplit = (T + tps - 1) / tps;
+}
+extern "C" int64_t vl2_attn_append_ws_bytes(int32_t P, int32_t n, int32_t nh) {
+    if (P < 0 || n <= 0 || nh <= 0) return 0;
+    const int64_t T = (P + (int64_t)n + 63) / 64;
+    return (int64_t)nh * n * (T < APPEND_MAX_SPLITS ? T : APPEND_MAX_SPLITS) * 130 * 4;
+}
+extern "C" int32_t vl2_attn_append(const void* q, int64_t q_rs, const void* kcache, const void* vcache, void* out, int64_t o_rs, int32_t P,
+                                   int32_t n, int32_t nh, int32_t nkv, int32_t smax, float scale, float* ws, int64_t ws_bytes, void* stream) {
+    if (!q || !kcache || !vcache || !out || !ws || n <= 0 || nh <= 0 || nkv <= 0 || smax <= 0 || P < 0)
+        return fail(VL2_E_BADARG, "vl2_attn_append: null pointer or empty shape");
+    if (nh % nkv) return fail(VL2_E_SHAPE, "vl2_attn_append: need nh = nkv*group");
+    if ((int64_t)P + n > smax) return fail(VL2_E_SHAPE, "vl2_attn_append: rows %d..%d outside the cache (%d)", P, P + n - 1, smax);
+    if (q_rs < (int64_t)nh * 128 || o_rs < (int64_t)nh * 128 || (q_rs & 7) || (o_rs & 7) || !ALIGNED16(q) || !ALIGNED16(kcache) || !ALIGNED16(vcache))
+        return fail(VL2_E_SHAPE, "vl2_attn_append: rows must hold nh*128 elements at 16-byte alignment");
+    if ((int64_t)smax * 128 * 2 >= (1ll << 31)) return fail(VL2_E_SHAPE, "vl2_attn_append: one head's cache spans >= 2 GiB");
+    if (ws_bytes < vl2_attn_append_ws_bytes(P, n, nh))
+        return fail(VL2_E_SHAPE, "vl2_attn_append: workspace of %lld bytes, need %lld", (long long)ws_bytes, (long long)vl2_attn_append_ws_bytes(P, n, nh));
+    const int group = nh / nkv;
+    int chunk, nsplit;
+    attn_append_split(P, n, group, nkv, chunk, nsplit);
+    AppendArgs a{(const bf16_t*)q, (long)q_rs, (const bf16_t*)kcache, (const bf16_t*)vcache, smax, P, n, nh, nkv, group, chunk, nsplit,
+                 scale * 1.4426950408889634f, ws};
+    hipLaunchKernelGGL(attn_append_kernel, dim3(nsplit, nkv, (n * group + 127) / 128), dim3(256), 0, ST(stream), a);
+    hipLaunchKernelGGL(attn_append_combine_kernel, dim3(nh, n), dim3(128), 0, ST(stream), (const float*)ws, (bf16_t*)out, (long)o_rs, n, P,
+                       chunk, nsplit);
+    return launched("vl2_attn_append");
 }
 extern "C" int32_t vl2_argmax(const float* logits, int32_t V, int32_t* tok, int32_t* hist, int32_t step, int32_t* state,
                               void* stream) {

@@ -60,6 +60,9 @@ class HipMistralDecoder(nn.Module):
         self.logits = torch.empty((self.V,), dtype=torch.float32, device=self._dev)
         self.graph = None
         self.pos = 0
+        # bumped by every call that rewrites the own KV cache (prefill, prefill_batch into it, extend) or changes the arithmetic of the
+        # rows a later call would append (fp8 toggles): a caller that recorded it can tell whether the rows it left are still there
+        self.cache_epoch = 0
         self._stage = None                  # (vl2_llm_desc, keepalive, decode workspace): prefill / decode step as ONE C call each
         # validation hook for 1-GPU boxes: issue the tensor-parallel all-reduces even when the group has ONE rank (the sum over one
         # rank is the identity), so that the captured-RCCL decode graph can be exercised on hardware without a second GPU
@@ -77,6 +80,7 @@ class HipMistralDecoder(nn.Module):
             self._make_w8()
         self.decode_fp8 = bool(on)
         self._invalidate_graphs()                                 # a captured step (greedy or sampled) holds the other projections
+        self.cache_epoch += 1
         return self
 
     def _make_w8(self):
@@ -105,6 +109,7 @@ class HipMistralDecoder(nn.Module):
         if on and getattr(self, "w8", None) is None:
             self._make_w8()
         self.prefill_fp8 = bool(on)
+        self.cache_epoch += 1
         return self
 
     def _stage_desc(self):
@@ -156,6 +161,8 @@ class HipMistralDecoder(nn.Module):
         if S > self.max_seq_len:
             raise ValueError(f"sequence length {S} exceeds the KV cache ({self.max_seq_len})")
         x = x.to(device=self._dev, dtype=_lib.elem_dtype()).contiguous()
+        if cache is None:
+            self.cache_epoch += 1
         if self._use_stage(cache) and not return_all_logits:      # the whole prefill as one call into libvl2hip.so (vl2_llm_prefill)
             out = self.logits if logits_out is None else logits_out
             ops.llm_prefill(self._stage_desc()[0], x, out, fp8=getattr(self, "prefill_fp8", False))
@@ -201,6 +208,64 @@ class HipMistralDecoder(nn.Module):
             return ops.gemm(h, self.w["lm_head"], out_f32=True)
         return ops.gemv(self.w["lm_head"], x[S - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True,
                         out=self.logits if logits_out is None else logits_out)
+
+    # ------------------------------------------------------------------ extend (prefill of new rows on top of the resident cache)
+    EXTEND_SKINNY_ROWS = 64      # up to this many rows the projections stream the weights once on the skinny-M kernel (ops.gemm_skinny)
+    EXTEND_APPEND_ROWS = 64      # up to this many rows the attention is vl2_attn_append (split-KV); beyond, vl2_attn_fwd with causal_off
+
+    @torch.no_grad()
+    def extend(self, x_new, start_pos=None, logits_out=None):
+        """Prefill of the rows start_pos .. start_pos + n - 1 (default start_pos = self.pos) against the single-sequence KV cache, whose
+        rows 0 .. start_pos - 1 must already hold the sequence (a previous prefill / extend / decode steps); rows from start_pos on are
+        overwritten.  x_new: inputs_embeds [n, D].  Leaves the last row's fp32 logits in self.logits (returned) and self.pos =
+        start_pos + n.  Per layer: q/k/v projection, RoPE + cache append at start_pos (ops.rope_kv), append attention
+        (ops.attn_append), then the family's `_extend_block_out` (Mixtral: its MoE block with S = n)."""
+        _lib.check_elem(self._elem, type(self).__name__)
+        if self.tp > 1 or self.tp_always_reduce:
+            raise NotImplementedError("extend: single-rank decoders only")
+        if getattr(self, "prefill_fp8", False):
+            raise NotImplementedError("extend runs the 16-bit projections: call enable_fp8_prefill(False) first")
+        P = self.pos if start_pos is None else int(start_pos)
+        n = x_new.shape[0]
+        if n <= 0:
+            raise ValueError("extend: no rows")
+        if P < 0 or P > self.pos:
+            raise ValueError(f"extend: start position {P} is not inside the resident cache (0 .. {self.pos})")
+        if P + n > self.max_seq_len:
+            raise ValueError(f"sequence length {P + n} exceeds the KV cache ({self.max_seq_len})")
+        self.cache_epoch += 1
+        x = x_new.to(device=self._dev, dtype=_lib.elem_dtype()).contiguous()
+        nh, nkv, hd, smax = self.nh, self.nkv, self.hd, self.max_seq_len
+        q = torch.empty((n, nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
+        o = torch.empty((n, nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
+        skinny = n <= self.EXTEND_SKINNY_ROWS
+        rs = ops.row_stats(x)
+        rn = ops.row_norm_finalize(rs, self.D, ops.NORM_RMS, self.eps)
+        for li, lw in enumerate(self.w["layers"]):
+            if skinny:
+                qkv = ops.gemm_skinny(ops.rmsnorm(x, self.w["ones"], self.eps), lw["wqkv"], bias=lw["bqkv"])
+            else:
+                qkv = ops.gemm(x, lw["wqkv"], bias=lw["bqkv"], norm=(ops.NORM_RMS, rn, self.eps, None))
+            ops.rope_kv(qkv, q, self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, nh, nkv, P)
+            if n <= self.EXTEND_APPEND_ROWS:
+                ops.attn_append(q, self.kcache[li], self.vcache[li], o, P, nh, nkv, hd ** -0.5)
+            else:
+                ops.attn_fwd(q, self.kcache[li], self.vcache[li], o, (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
+                             (0, hd, nh * hd), 1, nh, n, P + n, nh // nkv, hd ** -0.5, True, P, hd)
+            x = self._extend_block_out(lw, o, x, rs, rn, skinny)
+        self.pos = P + n
+        self.last_hidden = x
+        return ops.gemv(self.w["lm_head"], x[n - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True,
+                        out=self.logits if logits_out is None else logits_out)
+
+    def _extend_block_out(self, lw, o, x, rs, rn, skinny):
+        """The rest of an extend layer after attention.  Few rows: o_proj, gate/up and down on the skinny-M kernel (RMSNorm as its own
+        launch, like the batched decode step); otherwise the prefill's tiled GEMMs (`_prefill_block_out`, which also leaves rn)."""
+        if not skinny:
+            return self._prefill_block_out(lw, o, x, rs, rn)
+        x1 = ops.gemm_skinny(o, lw["wo"], res=x)
+        a = ops.gemm_skinny(ops.rmsnorm(x1, self.w["ones"], self.eps), lw["wgu"], swiglu=True)
+        return ops.gemm_skinny(a, lw["wd"], res=x1)
 
     def _prefill_block_out(self, lw, o, x, rs, rn):
         """The rest of a prefill layer after attention: x + o_proj(o), then the MLP (SwiGLU) with its residual; leaves (0, rstd) of
@@ -302,7 +367,7 @@ class HipMistralDecoder(nn.Module):
 
     @torch.no_grad()
     def generate(self, inputs_embeds, max_new_tokens=2048, eos_token_id=None, stopping_criteria=None,
-                 return_logits=False, use_graph=False, streamer=None, sampler=None):
+                 return_logits=False, use_graph=False, streamer=None, sampler=None, start_pos=None):
         """Greedy decode (HF GenerationMixin._sample, do_sample=False): returns LongTensor [1, n_new] of NEW tokens.
         Stops at `eos_token_id` (int or list), when `stopping_criteria(output_ids, None)` is truthy
         (KeywordsStoppingCriteria semantics, videollama2/mm_utils.py:341-345), or at max_new_tokens / cache end.
@@ -311,11 +376,16 @@ class HipMistralDecoder(nn.Module):
         uses with TextIteratorStreamer, serve/model_worker.py:263-300): every new token is handed over as soon as it is known.
         sampler = (temperature, top_k, top_p[, generator]): HF `_sample` with do_sample=True -- the logits warpers in HF's order and one draw per
         step (ops.sample_token, csrc/k_sample.h) instead of the argmax; the uniform numbers come from torch's generator for this device (or the
-        given one), so `torch.manual_seed` makes a run repeatable like it does for the reference."""
+        given one), so `torch.manual_seed` makes a run repeatable like it does for the reference.
+        start_pos: None = prefill `inputs_embeds` from position 0 (the plain path); an int = the cache already holds the sequence's rows
+        0 .. start_pos - 1 and `inputs_embeds` are its rows from start_pos on (`extend`), then the same decode loop."""
         eos = set()
         if eos_token_id is not None:
             eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
-        logits = self.prefill(inputs_embeds)
+        if start_pos is None:
+            logits = self.prefill(inputs_embeds)
+        else:
+            logits = self.extend(inputs_embeds, start_pos=start_pos)
         if logits.data_ptr() != self.logits.data_ptr():
             self.logits.copy_(logits)
         max_new_tokens = min(max_new_tokens, self.max_seq_len - self.pos + 1)
@@ -378,6 +448,8 @@ class HipMistralDecoder(nn.Module):
         lens = [x.shape[0] for x in xs]
         if max(lens) > self.max_seq_len:
             raise ValueError(f"sequence length {max(lens)} exceeds the KV cache ({self.max_seq_len})")
+        if any(len(kc) and kc[0] is self.kcache[0] for kc, _ in caches):
+            self.cache_epoch += 1
         X = torch.cat([x.to(device=self._dev, dtype=_lib.elem_dtype()) for x in xs], 0).contiguous()
         offs = [0]
         for n in lens:
@@ -656,6 +728,10 @@ class HipMixtralDecoder(HipMistralDecoder):
     def _prefill_block_out(self, lw, o, x, rs, rn):
         """x1 = x + o_proj(o) (its norm is taken by the router), then the sparse MoE block; the combine leaves (0, rstd) in `rn`."""
         return self.moe_block(lw, ops.gemm(o, lw["wo"], res=x), rn)
+
+    def _extend_block_out(self, lw, o, x, rs, rn, skinny):
+        """The MoE block of the prefill with S = n rows (the router, grouping and grouped GEMMs take any row count)."""
+        return self._prefill_block_out(lw, o, x, rs, rn)
 
     def _decode_block_out(self, lw, x):
         """x1 = x + o_proj(o); router GEMV (+RMSNorm, softmax, top-k -> ids / weights on the device); gate/up+SwiGLU GEMV of the k chosen

@@ -225,7 +225,10 @@ class VideoLLaMA2Hip(nn.Module):
     # ---------------------------------------------------------------------------------- videollama2_mistral.py:110-144
     @torch.no_grad()
     def generate(self, inputs=None, images=None, **kwargs):
+        """prefix_cache=True (batch 1, opt-in): reuse the decoder's KV rows left by the previous prefix-cache call for the longest common
+        prefix of the two prompts (see `_generate_prefix_cached`); `self.prefix_cache_stats` tells what the call reused."""
         kwargs.pop("position_ids", None)
+        prefix_cache = bool(kwargs.pop("prefix_cache", False))
         attention_mask = kwargs.pop("attention_mask", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")                # videollama2_mistral.py:119-120
@@ -253,15 +256,12 @@ class VideoLLaMA2Hip(nn.Module):
             sampler = (temperature, top_k, top_p, kwargs.get("generator", None))
         if inputs.dim() == 1:
             inputs = inputs[None]
+        if prefix_cache:
+            return self._generate_prefix_cached(inputs, images, attention_mask, sampler, kwargs)
         emb, lens = self._inputs_embeds(inputs, attention_mask, images)
         max_new, eos = kwargs.get("max_new_tokens", 2048), kwargs.get("eos_token_id", None)
         if emb.shape[0] == 1:
-            return self.decoder.generate(emb[0, :lens[0]], max_new_tokens=max_new, eos_token_id=eos,
-                                         stopping_criteria=kwargs.get("stopping_criteria", None),
-                                         return_logits=kwargs.get("return_logits", False), streamer=kwargs.get("streamer", None), sampler=sampler,
-                                         # one captured hipGraph per token by default (what bench.py measures); `use_graph=False`
-                                         # keeps the eager launch loop
-                                         use_graph=kwargs.get("use_graph", self._dev.type == "cuda" and self.decoder.tp == 1))
+            return self.decoder.generate(emb[0, :lens[0]], **self._decode_kwargs(kwargs, sampler))
         # batch > 1 (right-padded, arch.py:227-261): the sequences decode together, each on its own cache / position; finished rows
         # are filled with pad_token_id like HF's generate does
         if kwargs.get("stopping_criteria") is not None or kwargs.get("streamer") is not None or kwargs.get("return_logits"):
@@ -274,6 +274,117 @@ class VideoLLaMA2Hip(nn.Module):
         for bi, o in enumerate(outs):
             res[bi, :o.numel()] = o
         return res
+
+    def _decode_kwargs(self, kwargs, sampler):
+        return dict(max_new_tokens=kwargs.get("max_new_tokens", 2048), eos_token_id=kwargs.get("eos_token_id", None),
+                    stopping_criteria=kwargs.get("stopping_criteria", None),
+                    return_logits=kwargs.get("return_logits", False), streamer=kwargs.get("streamer", None), sampler=sampler,
+                    # one captured hipGraph per token by default (what bench.py measures); `use_graph=False` keeps the eager launch loop
+                    use_graph=kwargs.get("use_graph", self._dev.type == "cuda" and self.decoder.tp == 1))
+
+    # ---------------------------------------------------------------------------------- prefix reuse across chat turns
+    @staticmethod
+    def _media_equal(a, b):
+        """(tensor, modal) pairs: equal modal, dtype, shape and contents."""
+        (ta, ma), (tb, mb) = a, b
+        return ma == mb and ta.dtype == tb.dtype and ta.shape == tb.shape and torch.equal(ta.to(tb.device), tb)
+
+    def _generate_prefix_cached(self, inputs, images, attention_mask, sampler, kwargs):
+        """Batch-1 generate that reuses the KV rows of the previous prefix-cache call (`self._prefix_rec`: the ids whose rows are resident,
+        the media and the visual features spliced for them, the decoder's cache_epoch).  The common prefix of the new and the recorded ids
+        is counted in cache rows (a modal sentinel = its visual rows; media count as equal when modal, shape and contents are).  When it
+        covers every sentinel of the new prompt, neither the tower nor the connector runs: only the rows after it are embedded and
+        prefilled on top of the cache (decoder.generate(start_pos=...) -> extend), backing off one row when the new prompt adds nothing.
+        Otherwise -- no record, another epoch (an intervening prefill), changed media -- the full path runs.  Both paths record the call."""
+        if inputs.shape[0] != 1:
+            raise NotImplementedError("prefix_cache=True: batch 1 only")
+        if self.decoder.tp > 1:
+            raise NotImplementedError("prefix_cache=True: single-rank decoders only (extend is not built for tensor parallelism)")
+        ids = inputs[0].detach().cpu()
+        if attention_mask is not None:                           # batch 1, right-padded: the real tokens are the leading ones
+            m = attention_mask.detach().cpu().bool()[0]
+            n = int(m.sum())
+            if n == 0 or not bool(m[:n].all()):
+                raise NotImplementedError("HIP path: only right-padded prompts (attention_mask = 1...1 0...0) are supported")
+            ids = ids[:n]
+        ids_l = ids.tolist()
+        sent = set(MODAL_INDEX_MAP.values())
+        n_sent = sum(1 for t in ids_l if t in sent)
+        media = list(images) if images is not None else []
+        rec = getattr(self, "_prefix_rec", None)
+        reused, feats = 0, None
+        if rec is not None and rec["epoch"] == self.decoder.cache_epoch and n_sent == len(media) and len(ids_l) > 1:
+            rows, t, mk = 0, 0, 0
+            old = rec["ids"]
+            while t < min(len(ids_l), len(old)):
+                a, b = ids_l[t], old[t]
+                if a != b:
+                    break
+                if a in sent:
+                    if mk >= len(rec["media"]) or not self._media_equal(media[mk], rec["media"][mk]):
+                        break
+                    rows += rec["feats"][mk].shape[0]
+                    mk += 1
+                else:
+                    rows += 1
+                t += 1
+            if mk == n_sent:                                     # every sentinel of the new prompt lies inside the common prefix
+                feats = rec["feats"][:n_sent]
+                total = len(ids_l) - n_sent + sum(f.shape[0] for f in feats)
+                reused = min(rows, total - 1)                    # at least one row to prefill: its logits start the decode
+        if reused > 0:
+            emb = self._embed_suffix(ids_l, feats, reused)
+            out = self.decoder.generate(emb, start_pos=reused, **self._decode_kwargs(kwargs, sampler))
+            self.prefix_cache_stats = dict(reused_rows=reused, prefilled_rows=emb.shape[0], encoder_ran=False)
+        else:
+            feats = None
+            if n_sent and images is not None and len(ids_l) > 1:
+                feats = self.encode_images_or_videos(images)
+                _, _, _, emb, _ = self.prepare_inputs_labels_for_multimodal(ids[None], None, None, None, images, mm_features=feats)
+                emb = emb[0]
+                feats = [feats[k] for k in range(n_sent)]
+            else:
+                emb = torch.empty((len(ids_l), self.decoder.D), dtype=_lib.elem_dtype(), device=self._dev)
+                self._embed_ids(ids.to(self._dev), emb)
+                n_sent, feats = 0, []
+            out = self.decoder.generate(emb, **self._decode_kwargs(kwargs, sampler))
+            self.prefix_cache_stats = dict(reused_rows=0, prefilled_rows=emb.shape[0], encoder_ran=n_sent > 0)
+        total = len(ids_l) - n_sent + sum(f.shape[0] for f in feats)
+        toks = (out[0] if isinstance(out, tuple) else out)[0].tolist()
+        resident = ids_l + toks[:max(self.decoder.pos - total, 0)]  # the decoder's rows: the prompt, then the tokens the decode steps fed
+        self._prefix_rec = dict(ids=resident, media=[(t.detach().clone(), m) for t, m in media[:n_sent]], feats=feats,
+                                epoch=self.decoder.cache_epoch)
+        return out
+
+    def _embed_suffix(self, ids_l, feats, start):
+        """Embedding rows start .. end of the spliced prompt `ids_l` (text tokens through embed_tokens, the rows of the k-th sentinel from
+        feats[k])."""
+        sent = set(MODAL_INDEX_MAP.values())
+        total = len(ids_l) - len(feats) + sum(f.shape[0] for f in feats)
+        emb = torch.empty((total - start, self.decoder.D), dtype=_lib.elem_dtype(), device=self._dev)
+        row, mk, run = 0, 0, []
+
+        def flush(end_row):
+            if run:
+                r0 = end_row - len(run)
+                self._embed_ids(torch.tensor(run, dtype=torch.int64).to(self._dev), emb[r0 - start:end_row - start])
+                run.clear()
+
+        for t in ids_l:
+            if t in sent:
+                flush(row)
+                f = feats[mk]
+                mk += 1
+                lo = max(start - row, 0)
+                if lo < f.shape[0]:
+                    emb[row + lo - start:row + f.shape[0] - start].copy_(f[lo:].to(_lib.elem_dtype()))
+                row += f.shape[0]
+            else:
+                if row >= start:
+                    run.append(t)
+                row += 1
+        flush(row)
+        return emb
 
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None):
         """Continuous batching over this model (serving.ModelBatcher): submit (input_ids, images) requests at any time, `step()`

@@ -443,6 +443,27 @@ def attn_decode_batched(qkv, kcache, vcache, cos_t, sin_t, partial, out, nh, nkv
     return out
 
 
+_APPEND_WS = {}
+
+
+def attn_append(q, kcache, vcache, out, P, nh, nkv, scale, ws=None):
+    """include/vl2hip.h vl2_attn_append: the n = q.shape[0] roped query rows q [n, nh*128] at positions P .. P+n-1 attend causally to the
+    P + n keys of one sequence's caches [nkv, smax, 128] (rows P .. P+n-1 already appended) -> out [n, nh*128].  ws: fp32 workspace of at
+    least vl2_attn_append_ws_bytes (default: one per device, grown on demand)."""
+    _chk(q, _lib.elem_dtype(), "q"); _chk(kcache, _lib.elem_dtype(), "kcache"); _chk(vcache, _lib.elem_dtype(), "vcache")
+    _chk(out, _lib.elem_dtype(), "out"); _chk(ws, torch.float32, "ws")
+    n = q.shape[0]
+    need = int(_lib.load().vl2_attn_append_ws_bytes(int(P), n, nh))
+    if ws is None:
+        key = str(q.device)
+        ws = _APPEND_WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _APPEND_WS[key] = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=q.device)
+    _lib.call("vl2_attn_append", _p(q), q.stride(0), _p(kcache), _p(vcache), _p(out), out.stride(0), int(P), n, nh, nkv, kcache.shape[-2],
+              float(scale), _p(ws), ws.numel() * 4, _stream())
+    return out
+
+
 def argmax(logits, tok, hist=None, step=0, state=None):
     _lib.call("vl2_argmax", _p(logits), logits.numel(), _p(tok), _p(hist), step, _p(state), _stream())
 
