@@ -327,6 +327,14 @@ int32_t vl2_argmax(const float* logits, int32_t V, int32_t* tok, int32_t* hist, 
  * the float keys; probability mass in 2^-40 fixed point: deterministic). */
 int32_t vl2_sample_token(const float* logits, int32_t V, float temperature, int32_t top_k, float top_p, const float* u, int32_t* tok, int32_t* hist,
                          int32_t step, int32_t* state, float* dbg, void* stream);
+/* The draws of nb independent rows in ONE launch (the batched decode step; one 1024-thread workgroup per row): row b = logits + b*ld_logits (fp32, V
+ * entries) with its own settings in device arrays.  temperature[b] <= 0: greedy, HF `_sample` with do_sample=False -- tok[b] = vl2_argmax's token, step[b]
+ * untouched.  temperature[b] > 0: do_sample=True with the warpers of vl2_sample_token (scores / temperature[b]; top_k[b] > 0: top-k, HF's
+ * TopKLogitsWarper; top_p[b] < 1: top-p, HF's TopPLogitsWarper; top_k[b] >= 0 and top_p[b] > 0 are the caller's to check), then the inverse-CDF draw at
+ * u[b*ld_u + step[b]] (a step at or past ld_u reads the row's last number) -- tok[b] = vl2_sample_token's token for that row and u, and step[b] advances
+ * by one.  Every setting lives on the device, so one captured graph replays for any mix of greedy and sampled rows.  ld_logits >= V, ld_u >= 1. */
+int32_t vl2_sample_tokens(const float* logits, int64_t ld_logits, int32_t V, int32_t nb, const float* temperature, const int32_t* top_k,
+                          const float* top_p, const float* u, int64_t ld_u, int32_t* step, int32_t* tok, void* stream);
 /* out[i,:] = table[ids[i],:]; ids int32 device.  embed_tokens in videollama2/model/videollama2_arch.py:203-220. */
 int32_t vl2_embed_rows(const int32_t* ids, const void* table, void* out, int32_t n, int32_t D, int32_t ldo, void* stream);
 

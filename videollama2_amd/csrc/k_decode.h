@@ -699,20 +699,11 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(const float* _
     attn_combine_head<false>(src, nsplit, d, wgt, red, out + (size_t)bseq * out_bs + h * 128, true);
 }
 
-// first index of the maximum of logits[V] (fp32) -> *tok (int32) and hist[step]; one block of 1024 threads.
-// state != null (hipGraph-replayable decode): step = state[1]; afterwards state[0] (position) and state[1] advance by one.
-// zero / nzero: int32 words this launch clears first (the ticket counters of the fused attention launches of the step that follows:
-// a kernel-side clear instead of a memset node, which replayed wrongly from a captured hipGraph for a 32-byte range on ROCm 7.2).
-// embed != null (the stage-level decode step): the block then copies row `tok` of the embedding table (D bf16) to x0 -- the
-// embed_rows launch that used to follow (every launch of the decode graph costs ~4.5 us whatever it does).
-__global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ logits, int V, int* __restrict__ tok,
-                                                      int* __restrict__ hist, int step, int* __restrict__ state,
-                                                      int* __restrict__ zero, int nzero, const bf16_t* __restrict__ embed,
-                                                      bf16_t* __restrict__ x0, int D) {
+// first index of the maximum of logits[V] (fp32), found by the calling 1024-thread workgroup: the body of argmax_kernel and of the greedy rows of
+// sample_rows_kernel (k_sample.h).  The index is returned in thread 0.
+__device__ __forceinline__ int argmax_row(const float* __restrict__ logits, int V) {
     __shared__ float bv[16];
     __shared__ int bi[16];
-    __shared__ int s_tok;
-    for (int i = threadIdx.x; i < nzero; i += 1024) zero[i] = 0;
     float best = -3.4e38f;
     int idx = 0x7fffffff;
     // eight independent loads per trip (the scalar loop was one L2 round trip per element: ~31 dependent trips for V = 32000, 12 us);
@@ -736,6 +727,24 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w)
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+    }
+    return idx;
+}
+
+// first index of the maximum of logits[V] (fp32) -> *tok (int32) and hist[step]; one block of 1024 threads.
+// state != null (hipGraph-replayable decode): step = state[1]; afterwards state[0] (position) and state[1] advance by one.
+// zero / nzero: int32 words this launch clears first (the ticket counters of the fused attention launches of the step that follows:
+// a kernel-side clear instead of a memset node, which replayed wrongly from a captured hipGraph for a 32-byte range on ROCm 7.2).
+// embed != null (the stage-level decode step): the block then copies row `tok` of the embedding table (D bf16) to x0 -- the
+// embed_rows launch that used to follow (every launch of the decode graph costs ~4.5 us whatever it does).
+__global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ logits, int V, int* __restrict__ tok,
+                                                      int* __restrict__ hist, int step, int* __restrict__ state,
+                                                      int* __restrict__ zero, int nzero, const bf16_t* __restrict__ embed,
+                                                      bf16_t* __restrict__ x0, int D) {
+    __shared__ int s_tok;
+    for (int i = threadIdx.x; i < nzero; i += 1024) zero[i] = 0;
+    const int idx = argmax_row(logits, V);
+    if (threadIdx.x == 0) {
         *tok = idx;
         s_tok = idx;
         if (state) {

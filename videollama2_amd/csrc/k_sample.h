@@ -21,6 +21,7 @@
 // (128 KB at V = 32000, 600 KB at 152064) stay in L2; a pass is V / 1024 coalesced loads per thread.
 #pragma once
 #include "dev_common.h"
+#include "k_decode.h"                                               // argmax_row: the greedy rows of sample_rows_kernel
 
 __device__ __forceinline__ uint32_t sample_key(float x) {          // monotonic: a < b  <=>  key(a) < key(b)  (no NaNs in logits)
     const uint32_t b = __builtin_bit_cast(uint32_t, x);
@@ -81,13 +82,18 @@ __device__ __forceinline__ void sample_find_bin(const unsigned long long* hist, 
     }
 }
 
-// CACHE: the scaled scores live in dynamic LDS (V * 4 bytes, V <= 32768: the 32000-token vocabularies) after pass A, so the ten later passes read LDS
-// instead of re-reading the logits from L2 and re-dividing them (153 -> ~60 us per token at V = 32000); larger vocabularies stream from L2.
+// The sampled token of ONE row of logits, drawn by the calling 1024-thread workgroup: the body of sample_token_kernel (one row per launch) and of
+// sample_rows_kernel (one row per workgroup), so both give the same token for the same row, settings and u.  u: the address of the uniform number
+// (read by thread 0 only); dbg as SampleArgs::dbg.  The token is returned in thread 0 (-1 in the others).
+// CACHE: the scaled scores live in dynamic LDS (sc: V * 4 bytes, V <= 32768: the 32000-token vocabularies) after pass A, so the ten later passes read
+// LDS instead of re-reading the logits from L2 and re-dividing them (153 -> ~60 us per token at V = 32000); larger vocabularies stream from L2.
+// Every float expression here is shared by the two kernels; reassociation is off so that -ffast-math cannot associate them differently in the two
+// inlined copies (the mass sums are integer and associative anyway).
 template <bool CACHE>
-__global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    float* sc = (float*)vl2_smem;
-    auto score = [&](int i) -> float { return CACHE ? sc[i] : VL2_FDIV_RN(p.logits[i], p.temperature); };
+__device__ __forceinline__ int sample_row(float* sc, const float* __restrict__ logits, int V, float T, int top_k, float top_p, const float* u_at,
+                                          float* dbg) {
+#pragma clang fp reassociate(off)
+    auto score = [&](int i) -> float { return CACHE ? sc[i] : VL2_FDIV_RN(logits[i], T); };
     __shared__ unsigned long long hist64[256];
     __shared__ float s_red[16];
     __shared__ uint32_t s_prefix;
@@ -95,13 +101,11 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
     __shared__ int s_sel, s_tok, s_kept;
     __shared__ unsigned long long s_m[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int V = p.V;
-    const float T = p.temperature;
     if (tid == 0) { s_kept = 0; s_tok = -1; }
     // ---- pass A: the maximum score (the softmax shift; also the last key of every descent)
     float mx = -3.4e38f;
     for (int i = tid; i < V; i += 1024) {
-        const float s0 = VL2_FDIV_RN(p.logits[i], T);
+        const float s0 = VL2_FDIV_RN(logits[i], T);
         if (CACHE) sc[i] = s0;
         mx = fmaxf(mx, s0);
     }
@@ -114,9 +118,9 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
     __syncthreads();
     // ---- top-k: the key of the k-th largest score by radix descent over COUNTS (from the top bin downwards)
     uint32_t key_lo = 0;                                            // kept: key >= key_lo
-    if (p.top_k > 0 && p.top_k < V) {
+    if (top_k > 0 && top_k < V) {
         uint32_t prefix = 0;
-        unsigned long long need = (unsigned long long)p.top_k;     // rank still to be found inside the current prefix
+        unsigned long long need = (unsigned long long)top_k;     // rank still to be found inside the current prefix
         for (int lvl = 3; lvl >= 0; --lvl) {
             if (tid < 256) hist64[tid] = 0ull;
             __syncthreads();
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
     {
         uint32_t prefix = 0;
         unsigned long long below = 0;                              // mass of the survivors with keys below the current prefix range
-        const bool want_p = p.top_p < 1.0f;
+        const bool want_p = top_p < 1.0f;
         for (int lvl = 3; lvl >= (want_p ? 0 : 3); --lvl) {
             if (tid < 256) hist64[tid] = 0ull;
             __syncthreads();
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
                     unsigned long long z = hist64[4 * lane] + hist64[4 * lane + 1] + hist64[4 * lane + 2] + hist64[4 * lane + 3];
                     z = __shfl(sample_wave_scan(z, lane), 63);
                     // (1 - top_p) in fp32 as HF forms it, times Z in double: the largest integer mass that still counts as "<= threshold"
-                    r = want_p ? (unsigned long long)((double)(1.0f - p.top_p) * (double)z) : 0ull;
+                    r = want_p ? (unsigned long long)((double)(1.0f - top_p) * (double)z) : 0ull;
                     if (lane == 0) { s_target = z; s_thr = r; }
                 }
                 unsigned d = 0;
@@ -212,8 +216,7 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
     if (tid == 0) {
         unsigned long long tot = 0;
         for (int w = 0; w < 16; ++w) tot += s_m[w];
-        const int step = p.state ? p.state[1] : p.step;
-        float u = p.u[step];
+        float u = *u_at;
         u = u < 0.f ? 0.f : (u >= 1.f ? 0.99999994f : u);
         unsigned long long tgt = (unsigned long long)((double)u * (double)tot);
         if (tgt >= tot) tgt = tot - 1;
@@ -226,7 +229,7 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
         s_sel = w;                                                   // the owning wave; the exclusive prefix of its first chunk in s_base
         s_base = acc;
         s_target = tgt;
-        if (p.dbg) { p.dbg[0] = (float)s_kept; p.dbg[1] = Z ? (float)((double)tot / (double)Z) : 1.f; p.dbg[3] = mx; }
+        if (dbg) { dbg[0] = (float)s_kept; dbg[1] = Z ? (float)((double)tot / (double)Z) : 1.f; dbg[3] = mx; }
     }
     __syncthreads();
     const unsigned long long excl_t = s_base + incl_w - mine;
@@ -248,13 +251,23 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
         s_tok = sel >= 0 ? sel : last;
     }
     __syncthreads();
+    int sel = -1;
     if (tid == 0) {
-        const int sel = s_tok;
-        *p.tok = sel;
-        if (p.dbg) {
+        sel = s_tok;
+        if (dbg) {
             const uint32_t kb = (key_lo & 0x80000000u) ? (key_lo & 0x7fffffffu) : ~key_lo;
-            p.dbg[2] = key_lo ? __builtin_bit_cast(float, kb) : -3.4e38f;
+            dbg[2] = key_lo ? __builtin_bit_cast(float, kb) : -3.4e38f;
         }
+    }
+    return sel;
+}
+
+template <bool CACHE>
+__global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
+    const int sel = sample_row<CACHE>((float*)vl2_smem, p.logits, p.V, p.temperature, p.top_k, p.top_p, p.u + (p.state ? p.state[1] : p.step), p.dbg);
+    if (threadIdx.x == 0) {
+        *p.tok = sel;
         if (p.state) {
             if (p.hist) p.hist[p.state[1]] = sel;
             p.state[0] += 1;
@@ -262,5 +275,41 @@ __global__ __launch_bounds__(1024) void sample_token_kernel(SampleArgs p) {
         } else if (p.hist) {
             p.hist[p.step] = sel;
         }
+    }
+}
+
+struct SampleRowsArgs {
+    const float* logits;          // [nb, ld_logits] fp32
+    long long ld_logits;
+    int V;
+    const float* temperature;     // [nb]: <= 0 = greedy row
+    const int* top_k;             // [nb]: 0 (or >= V) = off
+    const float* top_p;           // [nb]: >= 1 = off
+    const float* u;               // [nb, ld_u]: row b consumes u[b * ld_u + step[b]]
+    long long ld_u;
+    int* step;                    // [nb]: advanced by one for every sampled row
+    int* tok;                     // [nb] -> the tokens
+};
+
+// The tokens of nb independent rows in ONE launch (grid = nb, one 1024-thread workgroup per row): the batched decode step's draw.  Row b reads its
+// settings and its step from device arrays, so one captured graph serves any mix of greedy and sampled requests.  A greedy row (temperature <= 0) is
+// argmax_row (the bits of argmax_kernel) and leaves step[b] alone; a sampled row is sample_row (the bits of sample_token_kernel) and advances step[b].
+template <bool CACHE>
+__global__ __launch_bounds__(1024) void sample_rows_kernel(SampleRowsArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
+    const int b = blockIdx.x;
+    const float* x = p.logits + (size_t)b * p.ld_logits;
+    const float T = p.temperature[b];
+    if (!(T > 0.f)) {
+        const int t = argmax_row(x, p.V);
+        if (threadIdx.x == 0) p.tok[b] = t;
+        return;
+    }
+    int s = p.step[b];
+    s = s < 0 ? 0 : (s < p.ld_u ? s : (int)(p.ld_u - 1));             // the row's last u once its numbers run out (never read out of the row)
+    const int t = sample_row<CACHE>((float*)vl2_smem, x, p.V, T, p.top_k[b], p.top_p[b], p.u + (size_t)b * p.ld_u + s, nullptr);
+    if (threadIdx.x == 0) {
+        p.tok[b] = t;
+        p.step[b] = s + 1;
     }
 }

@@ -1415,6 +1415,23 @@ extern "C" int32_t vl2_sample_token(const float* logits, int32_t V, float temper
     }
     return launched("vl2_sample_token");
 }
+// The draws of a batched decode step in ONE launch: row b of the logits is greedy (temperature[b] <= 0: vl2_argmax's token) or sampled (vl2_sample_token's
+// token at u[b * ld_u + step[b]], then step[b] += 1); every setting lives on the device, so one captured graph serves any mix (k_sample.h sample_rows_kernel).
+extern "C" int32_t vl2_sample_tokens(const float* logits, int64_t ld_logits, int32_t V, int32_t nb, const float* temperature, const int32_t* top_k,
+                                     const float* top_p, const float* u, int64_t ld_u, int32_t* step, int32_t* tok, void* stream) {
+    if (!logits || !temperature || !top_k || !top_p || !u || !step || !tok) return fail(VL2_E_BADARG, "vl2_sample_tokens: null pointer");
+    if (V <= 0 || nb <= 0) return fail(VL2_E_BADARG, "vl2_sample_tokens: need V > 0 and nb > 0 (got %d, %d)", V, nb);
+    if (ld_logits < V || ld_u < 1)
+        return fail(VL2_E_BADARG, "vl2_sample_tokens: need ld_logits >= V and ld_u >= 1 (got %lld, %lld)", (long long)ld_logits, (long long)ld_u);
+    SampleRowsArgs a{logits, ld_logits, V, temperature, top_k, top_p, u, ld_u, step, tok};
+    if (V <= 32768) {                  // as vl2_sample_token: the scaled scores of a row in LDS, one row per CU
+        lds_attr<sample_rows_kernel<true>>(32768 * 4);
+        hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(nb), dim3(1024), (size_t)V * 4, ST(stream), a);
+    } else {
+        hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(nb), dim3(1024), 0, ST(stream), a);
+    }
+    return launched("vl2_sample_tokens");
+}
 // the decode step's argmax, which also clears `nzero` int32 words (the fused attention launches' ticket counters)
 static int32_t argmax_and_clear(const float* logits, int32_t V, int32_t* tok, int32_t* hist, int32_t* state, int32_t* zero, int32_t nzero,
                                 const void* embed, void* x0, int32_t D, void* stream) {

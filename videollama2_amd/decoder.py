@@ -497,7 +497,11 @@ class HipMistralDecoder(nn.Module):
             x0=torch.empty((B, self.D), **bf), x1=torch.empty((B, self.D), **bf), qkv=torch.empty((B, (self.nh + 2 * self.nkv) * self.hd), **bf),
             o=torch.empty((B, self.nh * self.hd), **bf), a=torch.empty((B, I), **bf),
             logits=torch.empty((B, self.V), dtype=torch.float32, device=self._dev),
-            tok=torch.zeros((B,), dtype=torch.int32, device=self._dev), pos=torch.zeros((B,), dtype=torch.int32, device=self._dev))
+            tok=torch.zeros((B,), dtype=torch.int32, device=self._dev), pos=torch.zeros((B,), dtype=torch.int32, device=self._dev),
+            # per-slot draw settings of the sampled step (ops.sample_tokens): temperature 0 = greedy; slot b draws at u[b, sstep[b]]
+            samp_T=torch.zeros((B,), dtype=torch.float32, device=self._dev), samp_k=torch.zeros((B,), dtype=torch.int32, device=self._dev),
+            samp_p=torch.ones((B,), dtype=torch.float32, device=self._dev), u=torch.zeros((B, smax + 1), dtype=torch.float32, device=self._dev),
+            sstep=torch.zeros((B,), dtype=torch.int32, device=self._dev))
         return self._bb
 
     PREFILL_GROUP_TOKENS = 8192   # rows prefilled in one pass (activation scratch: ~0.6 GB at 7B widths)
@@ -563,36 +567,47 @@ class HipMistralDecoder(nn.Module):
         ops.gemv_batched(self.w["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=bb["logits"][:nb])
         bb["pos"][:nb] += 1
 
-    @torch.no_grad()
-    def _batched_step(self, nb):
+    def _sample_rows(self, nb):
+        """The draws of slots 0 .. nb-1 in ONE launch from their per-slot settings (samp_T / samp_k / samp_p, u, sstep): greedy slots take the
+        argmax, sampled ones draw and advance their sstep."""
         bb = self._bb
-        for b in range(nb):
-            ops.argmax(bb["logits"][b], bb["tok"][b:b + 1])
+        ops.sample_tokens(bb["logits"][:nb], bb["samp_T"], bb["samp_k"], bb["samp_p"], bb["u"], bb["sstep"], bb["tok"])
+
+    @torch.no_grad()
+    def _batched_step(self, nb, sampled=False):
+        bb = self._bb
+        if sampled:
+            self._sample_rows(nb)
+        else:
+            for b in range(nb):
+                ops.argmax(bb["logits"][b], bb["tok"][b:b + 1])
         self._decode_kernels_batched(nb)
 
-    def capture_batch_graph(self, nb):
-        """{argmax per request + the whole batched decode step} as ONE hipGraph per batch size (tokens and positions live on
-        the device, so the same graph replays for every step)."""
+    def capture_batch_graph(self, nb, sampled=False):
+        """{the draws + the whole batched decode step} as ONE hipGraph per (batch size, sampled) (tokens, positions and the
+        draw settings live on the device, so the same graph replays for every step).  sampled=False: one argmax launch per
+        request; sampled=True: one ops.sample_tokens launch for all nb rows, whatever mix of greedy and sampled slots they hold."""
         graphs = self.__dict__.setdefault("_batch_graphs", {})
-        if nb in graphs:
-            return graphs[nb]
+        key = (nb, bool(sampled))
+        if key in graphs:
+            return graphs[key]
         if self.tp > 1:
             raise NotImplementedError("hipGraph decode is built for the single-GPU decoder (collectives are launched eagerly)")
         bb = self._bb
-        saved = (bb["tok"].clone(), bb["pos"].clone(), bb["logits"].clone())
+        saved = (bb["tok"].clone(), bb["pos"].clone(), bb["logits"].clone(), bb["sstep"].clone())
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                       # warm-up outside capture (first-launch attribute calls, allocator)
-            self._batched_step(nb)
+            self._batched_step(nb, sampled)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        bb["pos"].copy_(saved[1])
+        bb["pos"].copy_(saved[1]); bb["sstep"].copy_(saved[3])
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._batched_step(nb)
-        bb["tok"].copy_(saved[0]); bb["pos"].copy_(saved[1]); bb["logits"].copy_(saved[2])
+            self._batched_step(nb, sampled)
+        bb["tok"].copy_(saved[0]); bb["pos"].copy_(saved[1]); bb["logits"].copy_(saved[2]); bb["sstep"].copy_(saved[3])
         torch.cuda.synchronize()
-        graphs[nb] = g
+        graphs[key] = g
         return g
 
     @torch.no_grad()
@@ -604,15 +619,17 @@ class HipMistralDecoder(nn.Module):
         LongTensor [n_new_b] (each ends at its EOS / max_new_tokens); with return_logits also the per-step fp32 logits
         [steps, B, V].  A row of a batched step is bit-identical to the single-sequence step while nb < GEMM_BATCH.
         use_graph (default: on a GPU without tensor parallelism) replays one captured hipGraph per step.
-        sampler = (temperature, top_k, top_p[, generator]): HF `_sample` with do_sample=True for every request -- one ops.sample_token launch per request
-        and step in place of its argmax (request b draws from its own row u[b, step] of uniform numbers, generated request by request from the
-        generator, so request 0's stream is the one a single-sequence `generate` with the same seed would use); the steps run eagerly."""
+        sampler = (temperature, top_k, top_p[, generator]): HF `_sample` with do_sample=True for every request -- ONE ops.sample_tokens launch per
+        step over all requests in place of their argmaxes (request b draws from its own row u[b, step] of uniform numbers, generated request by
+        request from the generator, so request 0's stream is the one a single-sequence `generate` with the same seed would use; its token is the
+        one ops.sample_token gives on its row); replayed from its own captured graph like the greedy step."""
         nb = len(inputs_embeds_list)
         if use_graph is None:
             use_graph = self._dev.type == "cuda" and self.tp == 1
         if sampler is not None:
-            use_graph = False
             T_, tk_, tp_ = float(sampler[0]), int(sampler[1]), float(sampler[2])
+            if not T_ > 0.0 or tk_ < 0 or not tp_ > 0.0:
+                raise ValueError(f"sampler: need temperature > 0, top_k >= 0, top_p > 0 (got {T_}, {tk_}, {tp_})")
             gen = sampler[3] if len(sampler) > 3 else None
             n_u = min(max_new_tokens, self.max_seq_len) + 1
             u_rows = torch.stack([torch.rand((n_u,), device=self._dev, generator=gen) for _ in range(nb)]).contiguous()
@@ -620,6 +637,10 @@ class HipMistralDecoder(nn.Module):
         if eos_token_id is not None:
             eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
         bb = self._ensure_batch(nb)
+        sampled = sampler is not None
+        if sampled:
+            bb["samp_T"][:nb].fill_(T_); bb["samp_k"][:nb].fill_(tk_); bb["samp_p"][:nb].fill_(tp_)
+            bb["u"][:nb, :n_u].copy_(u_rows); bb["sstep"][:nb].zero_()
         # prompts are prefilled together in groups of <= PREFILL_GROUP_TOKENS rows (bit-identical to one by one)
         lens, group, gtok = [], [], 0
         caches = [([k[b] for k in bb["k"]], [v[b] for v in bb["v"]]) for b in range(nb)]
@@ -642,7 +663,7 @@ class HipMistralDecoder(nn.Module):
         max_new_tokens = min(max_new_tokens, self.max_seq_len - max(lens) + 1)
         outs, done, all_logits = [[] for _ in range(nb)], [False] * nb, []
         use_graph = use_graph and max(lens) < self.max_seq_len          # a full cache leaves nothing to replay (see generate)
-        graph = self.capture_batch_graph(nb) if use_graph else None
+        graph = self.capture_batch_graph(nb, sampled) if use_graph else None
         if graph is not None:                                                # capture clobbered nothing: state was restored
             bb["pos"][:nb].copy_(torch.tensor(lens, dtype=torch.int32))
         for step in range(max_new_tokens):
@@ -650,10 +671,9 @@ class HipMistralDecoder(nn.Module):
                 all_logits.append(bb["logits"][:nb].clone())
             last = step + 1 == max_new_tokens
             if graph is not None and not last:
-                graph.replay()                                               # argmax(step) + forward of the new tokens
-            elif sampler is not None:
-                for b in range(nb):
-                    ops.sample_token(bb["logits"][b], bb["tok"][b:b + 1], u_rows[b], T_, tk_, tp_, step=step)
+                graph.replay()                                               # draws(step) + forward of the new tokens
+            elif sampled:
+                self._sample_rows(nb)
             else:
                 for b in range(nb):
                     ops.argmax(bb["logits"][b], bb["tok"][b:b + 1])

@@ -18,6 +18,36 @@ from .dist import FrameSharder
 from .tower import HipCLIPVisionTower, HipSiglipVisionTower
 
 
+# the warpers HF's `generate` could build from a sampling request, with their neutral values: this path builds temperature / top_k / top_p only
+UNBUILT_WARPERS = (("repetition_penalty", 1.0), ("min_p", None), ("typical_p", 1.0), ("epsilon_cutoff", 0.0), ("eta_cutoff", 0.0),
+                   ("no_repeat_ngram_size", 0), ("num_beams", 1))
+
+
+def resolve_sampler(kwargs, generation_config=None):
+    """The draw settings of a `generate`-style call: None for greedy decoding (do_sample False / absent), else (temperature, top_k, top_p, generator).
+    HF GenerationMixin.generate -> _get_logits_processor: temperature (default 1.0), top_k (generation_config default 50), top_p (default
+    1.0) as warpers in that order, then one multinomial draw per step (videollama2/__init__.py:93-106 passes temperature and top_p)
+    An unspecified value comes from the checkpoint's generation_config when the model carries one (`self.generation_config`, set by the loader
+    from generation_config.json like HF's from_pretrained does), else from HF's GenerationConfig defaults.  Warpers this path does not build are
+    refused instead of silently skipped (a checkpoint that sets them would be sampled from another kept set than the reference's)."""
+    if not kwargs.get("do_sample", False):
+        return None
+    gc = generation_config
+    gcv = lambda k, dflt: getattr(gc, k, None) if (gc is not None and getattr(gc, k, None) is not None) else dflt
+    for k, neutral in UNBUILT_WARPERS:
+        val = kwargs.get(k, gcv(k, neutral))
+        if val is not None and val != neutral:
+            raise NotImplementedError(f"HIP path: do_sample with {k}={val} is not built (temperature / top_k / top_p are)")
+    temperature, top_k, top_p = kwargs.get("temperature", gcv("temperature", 1.0)), kwargs.get("top_k", gcv("top_k", 50)), kwargs.get("top_p", gcv("top_p", 1.0))
+    temperature = 1.0 if temperature is None else float(temperature)
+    top_k, top_p = (0 if top_k is None else int(top_k)), (1.0 if top_p is None else float(top_p))
+    if not temperature > 0.0:
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")       # HF TemperatureLogitsWarper.__init__
+    if top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise ValueError(f"`top_k` has to be >= 0 and `top_p` a float > 0 and <= 1, but are {top_k} / {top_p}")
+    return (temperature, top_k, top_p, kwargs.get("generator", None))
+
+
 class VideoLLaMA2Hip(nn.Module):
     def __init__(self, cfg, state_dict, device="cuda", max_seq_len=4096, image_processor=None, n_llm_layers=None,
                  mm_projector_type=None, sharder=None, tp_group=None):
@@ -232,28 +262,7 @@ class VideoLLaMA2Hip(nn.Module):
         attention_mask = kwargs.pop("attention_mask", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")                # videollama2_mistral.py:119-120
-        sampler = None
-        if kwargs.get("do_sample", False):
-            # HF GenerationMixin.generate -> _get_logits_processor: temperature (default 1.0), top_k (generation_config default 50), top_p (default
-            # 1.0) as warpers in that order, then one multinomial draw per step (videollama2/__init__.py:93-106 passes temperature and top_p)
-            # An unspecified value comes from the checkpoint's generation_config when the model carries one (`self.generation_config`, set by the loader
-            # from generation_config.json like HF's from_pretrained does), else from HF's GenerationConfig defaults.  Warpers this path does not build are
-            # refused instead of silently skipped (a checkpoint that sets them would be sampled from another kept set than the reference's).
-            gc = getattr(self, "generation_config", None)
-            gcv = lambda k, dflt: getattr(gc, k, None) if (gc is not None and getattr(gc, k, None) is not None) else dflt
-            for k, neutral in (("repetition_penalty", 1.0), ("min_p", None), ("typical_p", 1.0), ("epsilon_cutoff", 0.0), ("eta_cutoff", 0.0),
-                               ("no_repeat_ngram_size", 0), ("num_beams", 1)):
-                val = kwargs.get(k, gcv(k, neutral))
-                if val is not None and val != neutral:
-                    raise NotImplementedError(f"HIP path: do_sample with {k}={val} is not built (temperature / top_k / top_p are)")
-            temperature, top_k, top_p = kwargs.get("temperature", gcv("temperature", 1.0)), kwargs.get("top_k", gcv("top_k", 50)), kwargs.get("top_p", gcv("top_p", 1.0))
-            temperature = 1.0 if temperature is None else float(temperature)
-            top_k, top_p = (0 if top_k is None else int(top_k)), (1.0 if top_p is None else float(top_p))
-            if not temperature > 0.0:
-                raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")       # HF TemperatureLogitsWarper.__init__
-            if top_k < 0 or not 0.0 < top_p <= 1.0:
-                raise ValueError(f"`top_k` has to be >= 0 and `top_p` a float > 0 and <= 1, but are {top_k} / {top_p}")
-            sampler = (temperature, top_k, top_p, kwargs.get("generator", None))
+        sampler = resolve_sampler(kwargs, getattr(self, "generation_config", None))
         if inputs.dim() == 1:
             inputs = inputs[None]
         if prefix_cache:
@@ -398,8 +407,7 @@ class VideoLLaMA2Hip(nn.Module):
         (input_ids [1, L] or [L], images) pairs exactly as `generate(inputs, images=...)` takes them one at a time.  Every
         request is encoded, spliced and prefilled on its own; the decode steps then run for all of them at once
         (`HipMistralDecoder.generate_batch`).  Returns a list of LongTensor [n_new] with the NEW tokens of each request."""
-        if kwargs.get("do_sample", False):
-            raise NotImplementedError("HIP path implements greedy decoding (do_sample=False, the reference default)")
+        sampler = resolve_sampler(kwargs, getattr(self, "generation_config", None))
         # video requests with the same frame count are encoded in ONE tower call (frames are an independent batch dim), the
         # connector then runs per video; every kernel involved is row-independent, so a request's tokens are the same as alone
         feats = {}
@@ -429,5 +437,5 @@ class VideoLLaMA2Hip(nn.Module):
                 embeds.append(emb)
         return self.decoder.generate_batch(embeds, max_new_tokens=kwargs.get("max_new_tokens", 2048),
                                            eos_token_id=kwargs.get("eos_token_id", None),
-                                           return_logits=kwargs.get("return_logits", False))
+                                           return_logits=kwargs.get("return_logits", False), sampler=sampler)
 

@@ -476,6 +476,24 @@ def sample_token(logits, tok, u, temperature, top_k=50, top_p=1.0, hist=None, st
               _p(state), _p(dbg), _stream())
 
 
+def sample_tokens(logits, temperature, top_k, top_p, u, step, tok):
+    """The draws of nb rows in ONE launch (include/vl2hip.h vl2_sample_tokens): logits [nb, V] fp32; per row temperature (fp32, <= 0 = greedy: the
+    `argmax` token), top_k (int32), top_p (fp32), its uniform numbers u [nb, n] (fp32, contiguous) and step (int32: a sampled row draws at
+    u[b, step[b]] -- `sample_token`'s token -- and advances it); tok [nb] int32 receives the tokens."""
+    _chk(logits, torch.float32, "logits"); _chk(temperature, torch.float32, "temperature"); _chk(top_k, torch.int32, "top_k")
+    _chk(top_p, torch.float32, "top_p"); _chk(u, torch.float32, "u"); _chk(step, torch.int32, "step"); _chk(tok, torch.int32, "tok")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [nb, V] with unit column stride")
+    nb = logits.shape[0]
+    if u.dim() != 2 or u.shape[0] < nb or u.stride(1) != 1 or u.stride(0) != u.shape[1]:
+        raise ValueError("u must be a contiguous [>= nb, n] tensor")
+    for t, n in ((temperature, "temperature"), (top_k, "top_k"), (top_p, "top_p"), (step, "step"), (tok, "tok")):
+        if t.dim() != 1 or t.numel() < nb or t.stride(0) != 1:
+            raise ValueError(f"{n} must be a contiguous vector of >= {nb} entries")
+    _lib.call("vl2_sample_tokens", _p(logits), logits.stride(0), logits.shape[1], nb, _p(temperature), _p(top_k), _p(top_p), _p(u), u.stride(0),
+              _p(step), _p(tok), _stream())
+
+
 def embed_rows(ids_i32, table, out):
     _lib.call("vl2_embed_rows", _p(ids_i32), _p(table), _p(out), ids_i32.numel(), table.shape[1], out.stride(0), _stream())
     return out

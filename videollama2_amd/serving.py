@@ -8,7 +8,10 @@ occupied slots (decoder._decode_kernels_batched), and between two steps
   * requests that hit EOS / a stop criterion / max_new_tokens / the cache end are retired (their streamer gets `end()`),
   * waiting requests are prefilled straight into a free slot's cache and join the next step.
 With at most 4 slots the step runs the multi-row GEMV whose rows are bit-identical to the single-sequence step, so a request's
-tokens do not depend on what else is in flight or when it was admitted (asserted in the tests)."""
+tokens do not depend on what else is in flight or when it was admitted (asserted in the tests).
+A request may sample (`submit(do_sample=True, ...)`, the worker's `temperature > 0.001` requests): its settings and its row of uniform numbers go
+into its slot at admission, and a step that holds any sampled request draws every slot's token in ONE ops.sample_tokens launch (greedy slots
+take the argmax there), so it still replays from one captured graph per occupancy."""
 import collections
 import itertools
 
@@ -16,10 +19,11 @@ import torch
 
 
 class _Request:
-    __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done")
+    __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done", "sampler", "u")
 
-    def __init__(self, rid, x, max_new, streamer, criteria):
+    def __init__(self, rid, x, max_new, streamer, criteria, sampler=None, u=None):
         self.rid, self.x, self.max_new, self.streamer, self.criteria = rid, x, max_new, streamer, criteria
+        self.sampler, self.u = sampler, u              # (temperature, top_k, top_p) and the request's uniform numbers, or None: greedy
         self.tokens, self.slot, self.done = [], None, False
 
 
@@ -44,16 +48,32 @@ class ContinuousBatcher:
         self.bb = decoder._ensure_batch(self.max_slots, owner=self)
 
     # ---- admission
-    def submit(self, inputs_embeds, max_new_tokens=2048, streamer=None, stopping_criteria=None):
+    def submit(self, inputs_embeds, max_new_tokens=2048, streamer=None, stopping_criteria=None, do_sample=False, temperature=None, top_k=None,
+               top_p=None, generator=None, **warpers):
         """Queue one request (inputs_embeds [S, D]: the spliced prompt of `prepare_inputs_labels_for_multimodal`).  It is prefilled
-        and joins the batch at the next `step()` with a free slot.  Returns the request id."""
+        and joins the batch at the next `step()` with a free slot.  Returns the request id.
+        do_sample=True: HF `_sample` with the warpers temperature -> top_k -> top_p, HF's defaults (1.0, 50, 1.0) for the unspecified ones and
+        HF's checks, as `VideoLLaMA2Hip.generate(do_sample=True)`; other warpers (`repetition_penalty`, ...) are refused unless neutral.  The
+        request's uniform numbers are drawn here from `generator` (or torch's generator for the device), as many and in the same call as a solo
+        `HipMistralDecoder.generate(sampler=...)` of this request draws them, so it samples the same tokens under the same seed."""
+        from .model import UNBUILT_WARPERS, resolve_sampler
+        unknown = set(warpers) - {k for k, _ in UNBUILT_WARPERS}
+        if unknown:
+            raise TypeError(f"submit() got unexpected keyword arguments {sorted(unknown)}")
+        given = dict(temperature=temperature, top_k=top_k, top_p=top_p, **warpers)
+        sampler = resolve_sampler(dict({k: v for k, v in given.items() if v is not None}, do_sample=do_sample, generator=generator))
         S = inputs_embeds.shape[0]
         if S > self.dec.max_seq_len:
             raise ValueError(f"sequence length {S} exceeds the KV cache ({self.dec.max_seq_len})")
         crit = stopping_criteria
         if crit is not None and not isinstance(crit, (list, tuple)):
             crit = [crit]
-        r = _Request(next(self._ids), inputs_embeds, min(int(max_new_tokens), self.dec.max_seq_len - S + 1), streamer, crit)
+        max_new = min(int(max_new_tokens), self.dec.max_seq_len - S + 1)
+        u = None
+        if sampler is not None:
+            u = torch.rand((max_new,), device=self.dec._dev, generator=sampler[3])
+            sampler = sampler[:3]
+        r = _Request(next(self._ids), inputs_embeds, max_new, streamer, crit, sampler, u)
         self.waiting.append(r)
         return r.rid
 
@@ -70,7 +90,12 @@ class ContinuousBatcher:
             dec.prefill(r.x, cache=cache, logits_out=bb["logits"][slot])          # fills rows [0, S) of the slot's cache
             dec.pos = own_pos
             bb["pos"][slot:slot + 1].fill_(r.x.shape[0])
-            r.slot, r.x = slot, None
+            T, k, p = r.sampler if r.sampler is not None else (0.0, 0, 1.0)                # temperature 0: a greedy slot
+            bb["samp_T"][slot:slot + 1].fill_(T); bb["samp_k"][slot:slot + 1].fill_(k); bb["samp_p"][slot:slot + 1].fill_(p)
+            bb["sstep"][slot:slot + 1].zero_()
+            if r.u is not None:
+                bb["u"][slot, :r.u.numel()].copy_(r.u)
+            r.slot, r.x, r.u = slot, None, None
             self.slots[slot] = r
 
     # ---- one decode step for everything in flight
@@ -89,12 +114,15 @@ class ContinuousBatcher:
         bb, dec = self.bb, self.dec
         nb = occupied[-1] + 1
         holes = [s for s in range(nb) if self.slots[s] is None]
-        if holes:            # an empty slot below the highest occupied one still computes (and is ignored): park it at position 0
-            bb["pos"][torch.tensor(holes, device=bb["pos"].device)] = 0
+        if holes:            # an empty slot below the highest occupied one still computes (and is ignored): park it at position 0, greedy
+            idx = torch.tensor(holes, device=bb["pos"].device)
+            bb["pos"][idx] = 0
+            bb["samp_T"][idx] = 0.0
+        sampled = any(self.slots[s].sampler is not None for s in occupied)
         if self.use_graph:
-            dec.capture_batch_graph(nb).replay()          # argmax of every slot's logits + the forward of the new tokens
+            dec.capture_batch_graph(nb, sampled).replay()     # the draws of every slot's logits + the forward of the new tokens
         else:
-            dec._batched_step(nb)
+            dec._batched_step(nb, sampled)
         self.steps += 1
         toks = bb["tok"][:nb].tolist()                    # one small D2H per step for the stop checks (as HF's loop does)
         out = {}
@@ -141,6 +169,14 @@ class ModelBatcher:
 
     @torch.no_grad()
     def submit(self, input_ids, images=None, attention_mask=None, **kw):
+        """Queue one request; the keywords are ContinuousBatcher.submit's, and unspecified sampling settings come from the model's
+        generation_config as in `VideoLLaMA2Hip.generate(do_sample=True)`."""
+        from .model import UNBUILT_WARPERS, resolve_sampler
+        sampler = resolve_sampler(kw, getattr(self.model, "generation_config", None))
+        for k in ("do_sample", "temperature", "top_k", "top_p", "generator") + tuple(k for k, _ in UNBUILT_WARPERS):
+            kw.pop(k, None)
+        if sampler is not None:
+            kw.update(do_sample=True, temperature=sampler[0], top_k=sampler[1], top_p=sampler[2], generator=sampler[3])
         ids = input_ids if input_ids.dim() == 2 else input_ids[None]
         emb, lens = self.model._inputs_embeds(ids, attention_mask, images)
         return self.inner.submit(emb[0, :lens[0]], **kw)
