@@ -266,6 +266,20 @@ int32_t vl2_gemm_skinny_bf16(const void* A, const void* W, void* C, const float*
 int32_t vl2_gemv_batched_bf16(const void* W, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
                               int32_t MB, int32_t N, int32_t K, int32_t ldw, int32_t ldx, int32_t ldy, int32_t ldres, float eps,
                               int32_t flags, void* stream);
+/* Batched decode on the fp8 weights of vl2_pack_quant_fp8 (W8A16: q [N, ldq] e4m3fn bytes, scale [N] power-of-two row scales, activations and
+ * products as vl2_gemv_fp8).  Additions of ABI 7.
+ * vl2_gemm_skinny_fp8: C[M <= 64, N] = scale[n] * (A q^T) (+bias | +res | SwiGLU | fp32 out), vl2_gemm_skinny_bf16's flags, checks and workspace;
+ *   bit for bit vl2_gemm_skinny_bf16 on the dequantised weights q * scale.  The K split depends on N and K only (a workspace too small for it is
+ *   refused, not worked round), so a row's result does not depend on the other rows.  N % 64 == 0, K % 32 == 0, ldq % 16 == 0.
+ * vl2_gemv_batched_fp8: y[b] = vl2_gemv_fp8 of row b for MB rows in one pass over q per launch (up to 4 rows, as many as fit 64 KiB of LDS;
+ *   larger MB is split); every row bit for bit the single-row call.  ldx / ldy / ldres = element strides between rows.  Flags as vl2_gemv_fp8
+ *   (VL2_GEMV_RMS_PLAIN included). */
+int32_t vl2_gemm_skinny_fp8(const void* A, const void* q, const float* scale, void* C, const float* bias, const void* res, int32_t M, int32_t N,
+                            int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws, int64_t ws_bytes,
+                            void* stream);
+int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
+                             int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps, int32_t flags,
+                             void* stream);
 /* Decode attention for ONE new token at position pos, fused with RoPE and the KV-cache append:
  *   qkv [(nh+2*nkv)*128] = un-roped fused q|k|v projection of the token; the kernel ropes q, ropes k and appends k,v to
  *   cache row pos (HF apply_rotary_pos_emb + DynamicCache.update), then softmax(q K^T / sqrt(d)) V over rows [0, pos]

@@ -242,3 +242,150 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(Gemv8Args p) {
         }
     }
 }
+
+// Multi-row form for BATCHED decode on the fp8 weights: y[b][:] = scale * (q x[b]) (+ bias) (+ res[b]) for MB = 2..4 sequences in one pass over
+// q -- what gemv_mr_bf16_kernel is to gemv_bf16_kernel.  Every row is gemv_fp8_kernel on that row, bit for bit: the same RMSNorm prologue (per
+// row, the same order), the same per-lane walk over the 16-B weight vectors (lane, lane + 64, ... whatever NP), the same dot2 sequence per pair
+// row, wave reduction, scale, SwiGLU pairing, bias and residual epilogue.  A weight dword is converted to element pairs ONCE and meets the MB x
+// vectors it serves.  x rows live in LDS as [MB][K] (MB * K * 2 <= 64 KiB: the launcher splits larger batches).  grid and NP as gemv_fp8_kernel.
+struct Gemv8MrArgs {
+    Gemv8Args g;            // W, scale, x (row 0), norm_w, res (row 0), y (row 0), N, K, ldw, eps, bias, rms_plain
+    int ldx, ldy, ldres;    // element strides between the rows of x / y / res
+};
+
+template <bool SWIGLU, bool OUT_F32, int NP, int MB>
+__global__ __launch_bounds__(256) void gemv_mr_fp8_kernel(Gemv8MrArgs pa) {
+#pragma clang fp reassociate(off)                  // the RMSNorm arithmetic in gemv_fp8_kernel's order
+    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
+    __shared__ float red[MB][4];
+    const Gemv8Args& p = pa.g;
+    bf16_t* xs = (bf16_t*)vl2_smem;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_pairs = p.N / 2;
+    const int nvec = p.K >> 4;
+    constexpr int SL = 8 / NP;
+    const bool one_pass = nvec <= 64 * SL;
+    u32x4 wv[8], uv[8];
+    const int jp0 = (blockIdx.x * 4 + wave) * NP;
+    auto rows_of = [&](int jp, int& r0, int& r1) {
+        r0 = SWIGLU ? (jp >> 5) * 64 + (jp & 31) : 2 * jp;
+        r1 = SWIGLU ? r0 + 32 : r0 + 1;
+    };
+    auto issue_rows = [&](int v0) {
+#pragma unroll
+        for (int pr = 0; pr < NP; ++pr) {
+            int r0, r1;
+            rows_of(jp0 + pr, r0, r1);
+            const uint8_t* w0p = p.W + (size_t)r0 * p.ldw;
+            const uint8_t* w1p = p.W + (size_t)r1 * p.ldw;
+            const bool live = jp0 + pr < n_pairs;
+#pragma unroll
+            for (int i = 0; i < SL; ++i) {
+                const int v = v0 + i * 64 + lane;
+                if (live && v < nvec) {
+                    wv[pr * SL + i] = __builtin_nontemporal_load((const u32x4*)(w0p + (size_t)v * 16));
+                    uv[pr * SL + i] = __builtin_nontemporal_load((const u32x4*)(w1p + (size_t)v * 16));
+                }
+            }
+        }
+    };
+    if (one_pass && jp0 < n_pairs) issue_rows(0);
+    float rstd[MB];
+#pragma unroll
+    for (int b = 0; b < MB; ++b) rstd[b] = 1.f;
+    const bool norm = p.norm_w != nullptr || p.rms_plain;
+    if (norm) {
+#pragma unroll
+        for (int b = 0; b < MB; ++b) {
+            float ss = 0.f;
+            for (int k = tid * 8; k < p.K; k += 2048) {
+                float v[8];
+                unpack8(*(const u32x4*)(p.x + (size_t)b * pa.ldx + k), v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) red[b][wave] = ss;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < MB; ++b) rstd[b] = rsqrtf(((red[b][0] + red[b][1]) + (red[b][2] + red[b][3])) / (float)p.K + p.eps);
+    }
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+        for (int k = tid * 8; k < p.K; k += 2048) {
+            u32x4 raw = *(const u32x4*)(p.x + (size_t)b * pa.ldx + k);
+            if (norm) {
+                float v[8];
+                unpack8(raw, v);
+                f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
+                if (p.norm_w) { w0 = *(const f32x4*)(p.norm_w + k); w1 = *(const f32x4*)(p.norm_w + k + 4); }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd[b]) * (j < 4 ? w0[j] : w1[j - 4]);
+                raw = pack8(v);
+            }
+            *(u32x4*)(xs + (size_t)b * p.K + k) = raw;
+        }
+    __syncthreads();
+    if (jp0 >= n_pairs) return;
+    float a0[NP][MB], a1[NP][MB];
+#pragma unroll
+    for (int pr = 0; pr < NP; ++pr)
+#pragma unroll
+        for (int b = 0; b < MB; ++b) a0[pr][b] = a1[pr][b] = 0.f;
+    for (int v0 = 0; v0 < nvec; v0 += 64 * SL) {
+        if (!one_pass) issue_rows(v0);
+#pragma unroll
+        for (int pr = 0; pr < NP; ++pr) {
+            if (jp0 + pr >= n_pairs) continue;
+#pragma unroll
+            for (int i = 0; i < SL; ++i) {
+                const int v = v0 + i * 64 + lane;
+                if (v < nvec) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const vl2_f32x2_t w0l = VL2_CVT_PK_F32_FP8(wv[pr * SL + i][q], false), w0h = VL2_CVT_PK_F32_FP8(wv[pr * SL + i][q], true);
+                        const vl2_f32x2_t w1l = VL2_CVT_PK_F32_FP8(uv[pr * SL + i][q], false), w1h = VL2_CVT_PK_F32_FP8(uv[pr * SL + i][q], true);
+                        const uint32_t e0l = pack2bf(w0l[0], w0l[1]), e0h = pack2bf(w0h[0], w0h[1]);
+                        const uint32_t e1l = pack2bf(w1l[0], w1l[1]), e1h = pack2bf(w1h[0], w1h[1]);
+#pragma unroll
+                        for (int b = 0; b < MB; ++b) {
+                            const u32x2 xq = *(const u32x2*)(xs + (size_t)b * p.K + (size_t)v * 16 + 4 * q);
+                            a0[pr][b] = dot2_bf16(e0l, xq[0], a0[pr][b]);
+                            a1[pr][b] = dot2_bf16(e1l, xq[0], a1[pr][b]);
+                            a0[pr][b] = dot2_bf16(e0h, xq[1], a0[pr][b]);
+                            a1[pr][b] = dot2_bf16(e1h, xq[1], a1[pr][b]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int pr = 0; pr < NP; ++pr) {
+        const int jp = jp0 + pr;
+        if (jp >= n_pairs) continue;
+        int r0, r1;
+        rows_of(jp, r0, r1);
+        float s0[MB], s1[MB];
+#pragma unroll
+        for (int b = 0; b < MB; ++b) { s0[b] = wave_sum(a0[pr][b]); s1[b] = wave_sum(a1[pr][b]); }
+        if (lane == 0) {
+#pragma unroll
+            for (int b = 0; b < MB; ++b) {
+                float t0 = s0[b] * p.scale[r0], t1 = s1[b] * p.scale[r1];
+                const bf16_t* res = p.res ? p.res + (size_t)b * pa.ldres : nullptr;
+                if (SWIGLU) {
+                    float o = silu_f(t0) * t1;
+                    if (res) o += bf2f(res[jp]);
+                    ((bf16_t*)p.y)[(size_t)b * pa.ldy + jp] = f2bf(o);
+                } else {
+                    if (p.bias) { t0 += p.bias[r0]; t1 += p.bias[r1]; }
+                    if (res) { t0 += bf2f(res[r0]); t1 += bf2f(res[r1]); }
+                    if (OUT_F32) { ((float*)p.y)[(size_t)b * pa.ldy + r0] = t0; ((float*)p.y)[(size_t)b * pa.ldy + r1] = t1; }
+                    else { ((bf16_t*)p.y)[(size_t)b * pa.ldy + r0] = f2bf(t0); ((bf16_t*)p.y)[(size_t)b * pa.ldy + r1] = f2bf(t1); }
+                }
+            }
+        }
+    }
+}

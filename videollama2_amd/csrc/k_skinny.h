@@ -87,10 +87,12 @@ struct SkinnyReduceArgs {
     const float* bias;      // [N] or null
     const bf16_t* res;      // [M, ldres] or null
     int M, Mp, N, KS, ldc, ldres;
+    const float* scale;     // [N] row scales of fp8 weights (SCALED only)
 };
 
-// one thread per 4 consecutive output columns of one row; SWIGLU: W packed in 64-row blocks {32 gate, 32 up}
-template <bool SWIGLU, bool OUT_F32>
+// one thread per 4 consecutive output columns of one row; SWIGLU: W packed in 64-row blocks {32 gate, 32 up}.  SCALED (the fp8 weights of
+// gemm_skinny_fp8_kernel): the ordered sum of GEMM column n is multiplied by scale[n] before the epilogue -- gate and up by their own rows'.
+template <bool SWIGLU, bool OUT_F32, bool SCALED = false>
 __global__ __launch_bounds__(256) void skinny_reduce_kernel(SkinnyReduceArgs p) {
     const int ncol = SWIGLU ? p.N / 2 : p.N;             // output columns
     const int per_row = ncol >> 2;
@@ -108,6 +110,13 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(SkinnyReduceArgs p) 
             const f32x4v b = *(const f32x4v*)(src + 32);
 #pragma unroll
             for (int j = 0; j < 4; ++j) u[j] += b[j];
+        }
+    }
+    if (SCALED) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            g[j] *= p.scale[n + j];
+            if (SWIGLU) u[j] *= p.scale[n + 32 + j];
         }
     }
     float o[4];

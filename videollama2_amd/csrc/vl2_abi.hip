@@ -30,6 +30,7 @@ static constexpr bool kLab = false;
 #include "k_pack.h"
 #include "k_sample.h"
 #include "k_skinny.h"
+#include "k_skinny_fp8.h"
 #include "k_stc.h"
 #include "k_vit.h"
 #include "k_moe.h"
@@ -923,6 +924,52 @@ extern "C" int32_t vl2_gemm_skinny_bf16(const void* A, const void* W, void* C, c
     return launched("vl2_gemm_skinny_bf16");
 }
 
+// fp8 weights (W8A16, k_skinny_fp8.h): the 16-bit launcher's grid, K chunking and reduce, the row scales applied in the reduce.  The K split
+// is chosen from N and K only -- never shrunk to fit the workspace, which is checked instead -- so a row's bits do not depend on M, and at the
+// decode shapes and the default workspace it is the 16-bit kernel's split (the output is vl2_gemm_skinny_bf16's on the dequantised weights).
+template <int MT>
+static void launch_skinny_fp8(const Skinny8Args& a, int ks, size_t lds, hipStream_t s) {
+    lds_attr<gemm_skinny_fp8_kernel<MT>>(65536);
+    hipLaunchKernelGGL((gemm_skinny_fp8_kernel<MT>), dim3(a.N / 64, ks), dim3(256), lds, s, a);
+}
+extern "C" int32_t vl2_gemm_skinny_fp8(const void* A, const void* q, const float* scale, void* C, const float* bias, const void* res, int32_t M,
+                                       int32_t N, int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws,
+                                       int64_t ws_bytes, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: null q (the e4m3fn weights)");
+    if (!scale) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: null scale (the weights' row scales)");
+    if (!A || !C || M <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: null pointer or empty shape");
+    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
+    if (M > 64) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: M=%d rows, need M<=64 (split larger batches)", M);
+    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
+    if (K % 32) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: need K%%32==0 (K=%d)", K);
+    if (lda % 8 || lda < K || ldq % 16 || ldq < K || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(q))
+        return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: need 16-byte aligned rows, lda%%8==0, ldq%%16==0, ldc%%4==0, ldres%%4==0");
+    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemm_skinny_fp8: SWIGLU excludes bias / f32 output");
+    if (!ws || !ALIGNED16(ws) || ws_bytes <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: needs a 16-byte aligned workspace (fp32 partial sums)");
+    const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4, Mp = 16 * mt;
+    const int steps = K / 32;
+    int ks = (4096 + N / 16 - 1) / (N / 16);
+    ks = ks < 1 ? 1 : ks > 32 ? 32 : ks;
+    while (ks > 1 && steps % ks) --ks;
+    if ((int64_t)ks * Mp * N * 4 > ws_bytes)
+        return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)ks * Mp * N * 4);
+    const int kslice = K / ks;
+    int kchunk = kslice;
+    while (kchunk > 32 && (kslice % kchunk || kchunk % 32 || (size_t)Mp * (kchunk + 8) * 2 > 65536)) kchunk -= 32;
+    if (kslice % kchunk || (size_t)Mp * (kchunk + 8) * 2 > 65536) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: no K chunking for K=%d", K);
+    Skinny8Args a{(const bf16_t*)A, (const uint8_t*)q, (float*)ws, M, N, K, lda, ldq, kslice, kchunk};
+    const size_t lds = (size_t)Mp * (kchunk + 8) * 2;
+    hipStream_t s = ST(stream);
+    if (mt == 1) launch_skinny_fp8<1>(a, ks, lds, s); else if (mt == 2) launch_skinny_fp8<2>(a, ks, lds, s); else launch_skinny_fp8<4>(a, ks, lds, s);
+    SkinnyReduceArgs r{(const float*)ws, C, bias, (const bf16_t*)res, M, Mp, N, ks, ldc, ldres, scale};
+    const int ncol = sw ? N / 2 : N;
+    const dim3 g((M * (ncol / 4) + 255) / 256), b(256);
+    if (sw) hipLaunchKernelGGL((skinny_reduce_kernel<true, false, true>), g, b, 0, s, r);
+    else if (f32) hipLaunchKernelGGL((skinny_reduce_kernel<false, true, true>), g, b, 0, s, r);
+    else hipLaunchKernelGGL((skinny_reduce_kernel<false, false, true>), g, b, 0, s, r);
+    return launched("vl2_gemm_skinny_fp8");
+}
+
 // ------------------------------------------------------------------------------------------------ norms
 static int32_t launch_norm(const NormArgs& a, bool rms, hipStream_t s, const char* what) {
     if (!a.x || !a.y || !a.w || a.rows <= 0 || a.C <= 0) return fail(VL2_E_BADARG, "%s: null pointer or empty shape", what);
@@ -1299,6 +1346,55 @@ extern "C" int32_t vl2_gemv_batched_bf16(const void* W, const void* x, const flo
         b0 += mb;
     }
     return launched("vl2_gemv_batched_bf16");
+}
+// fp8 weights: rows of K <= 4096 two pairs per wave (NP = 2) as vl2_gemv_fp8; MB = 1 IS gemv_fp8_kernel, MB = 2..4 gemv_mr_fp8_kernel (k_fp8.h)
+template <bool SW, bool F32>
+static void launch_gemv_fp8_rows(const Gemv8MrArgs& a, int mb, hipStream_t s) {
+    const int N = a.g.N, K = a.g.K;
+    const size_t lds = (size_t)mb * K * 2;
+    const dim3 b(256);
+    if (K <= 4096) {
+        const dim3 g((unsigned)((N / 2 + 7) / 8));
+        if (mb == 1) hipLaunchKernelGGL((gemv_fp8_kernel<SW, F32, 2>), g, b, lds, s, a.g);
+        else if (mb == 2) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 2, 2>), g, b, lds, s, a);
+        else if (mb == 3) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 2, 3>), g, b, lds, s, a);
+        else hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 2, 4>), g, b, lds, s, a);
+    } else {
+        const dim3 g((unsigned)((N / 2 + 3) / 4));
+        if (mb == 1) hipLaunchKernelGGL((gemv_fp8_kernel<SW, F32, 1>), g, b, lds, s, a.g);
+        else if (mb == 2) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 1, 2>), g, b, lds, s, a);
+        else if (mb == 3) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 1, 3>), g, b, lds, s, a);
+        else hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 1, 4>), g, b, lds, s, a);
+    }
+}
+extern "C" int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias,
+                                        void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps,
+                                        int32_t flags, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "vl2_gemv_batched_fp8: null q (the e4m3fn weights)");
+    if (!scale) return fail(VL2_E_BADARG, "vl2_gemv_batched_fp8: null scale (the weights' row scales)");
+    if (!x || !y || N <= 0 || K <= 0 || MB <= 0) return fail(VL2_E_BADARG, "vl2_gemv_batched_fp8: null pointer or empty shape");
+    if (K % 16 || K > 32704) return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: need K%%16==0, K<=32704 (x lives in LDS as 16-bit elements; K=%d)", K);
+    if (N % 2) return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: need N even (N=%d)", N);
+    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
+    const int n_out = sw ? N / 2 : N;
+    if (ldq % 16 || ldq < K || ldx % 8 || ldx < K || ldy < n_out || (res && (ldres < n_out)) || !ALIGNED16(q) || !ALIGNED16(x))
+        return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: need 16-byte aligned rows, ldq%%16==0, ldq>=K, ldx%%8==0, ldx>=K, ldy / ldres >= the output width");
+    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemv_batched_fp8: SWIGLU excludes bias / f32 output");
+    if (sw && N % 64) return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: SWIGLU needs N%%64==0 (N=%d)", N);
+    const int esz = f32 ? 4 : 2;
+    const int cap = 65536 / (K * 2) < 4 ? 65536 / (K * 2) : 4;        // x rows that fit the 64 KiB of LDS, at most 4 per pass
+    const bool plain = flags & VL2_GEMV_RMS_PLAIN;
+    for (int b0 = 0; b0 < MB;) {
+        const int mb = MB - b0 < cap ? MB - b0 : cap;
+        Gemv8MrArgs a{{(const uint8_t*)q, scale, (const bf16_t*)x + (size_t)b0 * ldx, plain ? nullptr : norm_w,
+                       res ? (const bf16_t*)res + (size_t)b0 * ldres : nullptr, (char*)y + (size_t)b0 * ldy * esz, N, K, ldq, eps, bias, plain ? 1 : 0},
+                      ldx, ldy, ldres};
+        if (sw) launch_gemv_fp8_rows<true, false>(a, mb, ST(stream));
+        else if (f32) launch_gemv_fp8_rows<false, true>(a, mb, ST(stream));
+        else launch_gemv_fp8_rows<false, false>(a, mb, ST(stream));
+        b0 += mb;
+    }
+    return launched("vl2_gemv_batched_fp8");
 }
 extern "C" int32_t vl2_attn_decode(const void* qkv, void* kcache, void* vcache, const float* cos_t, const float* sin_t,
                                    float* partial, void* out, int32_t nh, int32_t nkv, int32_t smax, int32_t pos,

@@ -93,9 +93,11 @@ class HipMistralDecoder(nn.Module):
 
     def _invalidate_graphs(self):
         """Drop every captured decode graph: the greedy one and the sampled one (keyed by the sampler only) both bake in the weight
-        pointers / arithmetic (`decode_fp8`) and the stage workspace of the moment they were captured."""
+        pointers / arithmetic (`decode_fp8`) and the stage workspace of the moment they were captured; so do the batched steps' graphs
+        (capture_batch_graph), which the next step captures again on the weights then selected."""
         self.graph = None
         self._graph_sample = (None, None)
+        self.__dict__.get("_batch_graphs", {}).clear()
 
     @torch.no_grad()
     def enable_fp8_prefill(self, on=True):
@@ -513,10 +515,10 @@ class HipMistralDecoder(nn.Module):
         nb < GEMM_BATCH: multi-row GEMV (a row is bit-identical to the single-sequence step).  nb >= GEMM_BATCH: the
         projections run on the skinny-M MFMA kernel (weights streamed once, GEMV-style, for up to 64 rows; the tiled GEMMs
         beyond that; RMSNorm as its own kernel) -- prefill-style arithmetic, i.e. equal to the single-sequence step to bf16
-        rounding, not to the bit."""
-        if getattr(self, "decode_fp8", False):
-            raise NotImplementedError("fp8 decode weights (enable_fp8_decode) cover the single-sequence decode step; batched decode streams "
-                                      "the 16-bit weights: call enable_fp8_decode(False) first")
+        rounding, not to the bit.
+        With enable_fp8_decode the same step streams the fp8 copies (W8A16): the multi-row fp8 GEMV below GEMM_BATCH (a row is bit-identical
+        to the single-sequence fp8 step), the fp8 skinny-M kernel from GEMM_BATCH on, in calls of at most 64 rows (bit-identical to the 16-bit
+        skinny-M step on the dequantised weights)."""
         bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
         x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
         ops.embed_rows(bb["tok"][:nb], self.w["embed"], x)
@@ -538,6 +540,9 @@ class HipMistralDecoder(nn.Module):
         bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
         x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
         r0 = self.tp_rank == 0
+        if getattr(self, "decode_fp8", False):
+            self._batched_gemm_step_fp8(nb)
+            return
         # up to 64 rows: the skinny-M kernel streams the weights GEMV-style into MFMA; beyond that the tiled GEMMs
         mm = ops.gemm_skinny if nb <= 64 else ops.gemm
         for li, lw in enumerate(self.w["layers"]):
@@ -553,10 +558,41 @@ class HipMistralDecoder(nn.Module):
         mm(h, self.w["lm_head"], out_f32=True, out=bb["logits"][:nb])
         bb["pos"][:nb] += 1
 
+    def _batched_gemm_step_fp8(self, nb):
+        """_batched_gemm_step on the fp8 copies: the skinny-M fp8 kernel for every projection and any nb (ops.gemm_skinny_fp8 runs more
+        than 64 rows in calls of at most 64, the weights streamed once per call); norms, bias and residual wiring as the 16-bit step.
+        (fp8 decode weights are single-rank: no all-reduce.)"""
+        bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
+        x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
+        for li, (lw, q) in enumerate(zip(self.w["layers"], self.w8["layers"])):
+            h = ops.rmsnorm(x, self.w["ones"], self.eps)                  # the norm weights are folded into wqkv / wgu (and their fp8 copies)
+            ops.gemm_skinny_fp8(h, *q["wqkv"], bias=lw["bqkv"], out=qkv)
+            ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
+                                    bb["pos"][:nb], self.max_seq_len, hd ** -0.5)
+            ops.gemm_skinny_fp8(o, *q["wo"], res=x, out=x1)
+            h = ops.rmsnorm(x1, self.w["ones"], self.eps)
+            ops.gemm_skinny_fp8(h, *q["wgu"], swiglu=True, out=a)
+            ops.gemm_skinny_fp8(a, *q["wd"], res=x1, out=x)
+        h = ops.rmsnorm(x, self.w["norm_w"], self.eps)
+        ops.gemm_skinny_fp8(h, *self.w8["lm_head"], out_f32=True, out=bb["logits"][:nb])
+        bb["pos"][:nb] += 1
+
     def _batched_gemv_step(self, nb):
         bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
         x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
         r0 = self.tp_rank == 0
+        if getattr(self, "decode_fp8", False):
+            # the single-sequence fp8 step (_decode_kernels) row by row: q/k/v and gate/up RMS-normalise x without a weight (folded into W)
+            for li, (lw, q) in enumerate(zip(self.w["layers"], self.w8["layers"])):
+                ops.gemv_batched_fp8(*q["wqkv"], x, eps=self.eps, out=qkv, bias=lw["bqkv"], rms_plain=True)
+                ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
+                                        bb["pos"][:nb], self.max_seq_len, hd ** -0.5)
+                ops.gemv_batched_fp8(*q["wo"], o, res=x, out=x1)
+                ops.gemv_batched_fp8(*q["wgu"], x1, eps=self.eps, swiglu=True, out=a, rms_plain=True)
+                ops.gemv_batched_fp8(*q["wd"], a, res=x1, out=x)
+            ops.gemv_batched_fp8(*self.w8["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=bb["logits"][:nb])
+            bb["pos"][:nb] += 1
+            return
         for li, lw in enumerate(self.w["layers"]):
             ops.gemv_batched(lw["wqkv"], x, norm_w=self.w["ones"], eps=self.eps, out=qkv, bias=lw["bqkv"])
             ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
@@ -586,7 +622,8 @@ class HipMistralDecoder(nn.Module):
     def capture_batch_graph(self, nb, sampled=False):
         """{the draws + the whole batched decode step} as ONE hipGraph per (batch size, sampled) (tokens, positions and the
         draw settings live on the device, so the same graph replays for every step).  sampled=False: one argmax launch per
-        request; sampled=True: one ops.sample_tokens launch for all nb rows, whatever mix of greedy and sampled slots they hold."""
+        request; sampled=True: one ops.sample_tokens launch for all nb rows, whatever mix of greedy and sampled slots they hold.
+        enable_fp8_decode(on / off) drops them all (_invalidate_graphs): the next step captures the weights then selected."""
         graphs = self.__dict__.setdefault("_batch_graphs", {})
         key = (nb, bool(sampled))
         if key in graphs:

@@ -418,6 +418,42 @@ def gemv_batched(w, x, norm_w=None, eps=1e-5, res=None, swiglu=False, out_f32=Fa
     return out
 
 
+def gemm_skinny_fp8(a, q, scale, bias=None, res=None, swiglu=False, out_f32=False, out=None):
+    """C = epilogue(scale * (a @ q.T)) on fp8 weights (include/vl2hip.h vl2_gemm_skinny_fp8; W8A16): q [N, K] e4m3fn bytes and scale [N] from
+    `quant_fp8`.  Bit for bit `gemm_skinny(a, dequant(q, scale))`.  More than 64 rows run as calls of at most 64 rows each (the weights stream
+    once per call; a row's bits do not depend on the chunk it lands in).  Needs `attach_workspace`."""
+    _chk(a, _lib.elem_dtype(), "a"); _chk(q, torch.uint8, "q"); _chk(scale, torch.float32, "scale"); _chk(bias, torch.float32, "bias")
+    _chk(res, _lib.elem_dtype(), "res")
+    M, K = a.shape
+    N = q.shape[0]
+    ncol = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((M, ncol), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=a.device)
+    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0)
+    ws = attach_workspace(a.device)
+    for m0 in range(0, M, 64):
+        m1 = min(M, m0 + 64)
+        _lib.call("vl2_gemm_skinny_fp8", _p(a[m0:m1]), _p(q), _p(scale), _p(out[m0:m1]), _p(bias), _p(None if res is None else res[m0:m1]),
+                  m1 - m0, N, K, a.stride(0), q.stride(0), out.stride(0), 0 if res is None else res.stride(0), flags, _p(ws), ws.numel(), _stream())
+    return out
+
+
+def gemv_batched_fp8(q, scale, x, norm_w=None, eps=1e-5, res=None, swiglu=False, out_f32=False, out=None, bias=None, rms_plain=False):
+    """y[b] = gemv_fp8(q, scale, x[b], ...) for the rows of x [MB, K] in one pass over q per launch of up to 4 rows (include/vl2hip.h
+    vl2_gemv_batched_fp8): every row bit for bit the single-row call.  res / out are [MB, n_out]."""
+    _chk(q, torch.uint8, "q"); _chk(scale, torch.float32, "scale"); _chk(x, _lib.elem_dtype(), "x"); _chk(bias, torch.float32, "bias")
+    _chk(res, _lib.elem_dtype(), "res")
+    N, K = q.shape
+    MB = x.shape[0]
+    n_out = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((MB, n_out), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
+    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    _lib.call("vl2_gemv_batched_fp8", _p(q), _p(scale), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), MB, N, K, q.stride(0), x.stride(0),
+              out.stride(0), 0 if res is None else res.stride(0), float(eps), flags, _stream())
+    return out
+
+
 def attn_decode(qkv, kcache, vcache, cos_t, sin_t, partial, out, nh, nkv, pos, scale, pos_dev=None, ctx_cap=0):
     """RoPE + KV append + flash-decoding attention of one new token (un-roped fused qkv row) at position `pos`
     (or *pos_dev, for hipGraph replay; then ctx_cap bounds the positions the launch covers)."""
