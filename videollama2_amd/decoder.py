@@ -12,6 +12,105 @@ from . import _lib, ops
 from .weights import pack_decoder
 
 
+def eos_set(eos_token_id):
+    """The stop ids of a decode loop: `eos_token_id` is None, one id, or a list / tuple / set of ids."""
+    if eos_token_id is None:
+        return set()
+    return set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
+
+
+# ---------------------------------------------------------------------- projection forms
+# A form is the kernel family that projects a layer's activations, picked once per call from the path and the fp8 switches.  The two
+# layer loops (HipMistralDecoder._rows / _tokens) ask it for normed(x, w) = RMSNorm(x) @ w.T (the norm weight is folded into w: q/k/v,
+# gate/up), res(a, w, x) = x + a @ w.T (o, down) and, in the token loop, head(x, out) = the fp32 logits.  `layers` holds the per-layer
+# weights it reads (the 16-bit dicts or their fp8 copies).  16-bit forms under tensor parallelism: the residual rides on rank 0's partial
+# sum and the result is all-reduced; the fp8 forms are single-rank and issue no all-reduce.
+class _Form:
+    def __init__(self, dec, fp8=False):
+        self.dec, self.fp8 = dec, fp8
+        w = dec.w8 if fp8 else dec.w
+        self.layers, self.lm_head = w["layers"], w["lm_head"]
+
+    def begin(self, x):
+        """The rows loop's prologue: (0, rstd) of x's rows in rn, which the carried norm reads and Mixtral's MoE combine keeps current."""
+        self.rs = ops.row_stats(x)
+        self.rn = ops.row_norm_finalize(self.rs, self.dec.D, ops.NORM_RMS, self.dec.eps)
+
+    def res(self, a, w, x, out=None):
+        if self.fp8:
+            return self._mm(a, w, res=x, out=out)
+        dec = self.dec
+        return dec._reduce(self._mm(a, w, res=x if dec.tp_rank == 0 else None, out=out))
+
+
+class _Tiled(_Form):
+    """The tiled MFMA GEMMs with the RMSNorm carried: each residual projection's epilogue emits its rows' statistics, reduced once into rn
+    for the next normed GEMM.  Tensor parallel: the GEMM output is a partial sum, so the statistics are taken after the all-reduce."""
+
+    def normed(self, x, w, bias=None, swiglu=False):
+        return ops.gemm(x, w, bias=bias, swiglu=swiglu, norm=(ops.NORM_RMS, self.rn, self.dec.eps, None), mfma16=swiglu)
+
+    def res(self, a, w, x):
+        dec = self.dec
+        if dec.tp > 1:
+            x = dec._reduce(ops.gemm(a, w, res=x if dec.tp_rank == 0 else None))
+            ops.row_stats(x, out=self.rs)
+        else:
+            x = ops.gemm(a, w, res=x, stats_out=self.rs)
+        ops.row_norm_finalize(self.rs, dec.D, ops.NORM_RMS, dec.eps, out=self.rn)
+        return x
+
+
+class _W8A8(_Form):
+    """fp8 weights and fp8 activations, quantised per row on the fly (with the row's RMS for a normed projection)."""
+
+    def __init__(self, dec):
+        super().__init__(dec, fp8=True)
+
+    def begin(self, x):
+        pass
+
+    def normed(self, x, w, bias=None, swiglu=False):
+        return ops.gemm_fp8(*ops.quant_act_fp8(x, rms_eps=self.dec.eps), *w, bias=bias, swiglu=swiglu)
+
+    def _mm(self, a, w, **kw):
+        return ops.gemm_fp8(*ops.quant_act_fp8(a), *w, **kw)
+
+
+class _Skinny(_Form):
+    """RMSNorm as its own launch, then the skinny-M MFMA kernel: the weights stream once for up to 64 rows (16-bit: the tiled GEMM
+    beyond; fp8: calls of at most 64 rows)."""
+
+    def __init__(self, dec, fp8, rows):
+        super().__init__(dec, fp8)
+        self._mm = (lambda a, w, **kw: ops.gemm_skinny_fp8(a, *w, **kw)) if fp8 else ops.gemm_skinny if rows <= 64 else ops.gemm
+
+    def normed(self, x, w, **kw):
+        return self._mm(ops.rmsnorm(x, self.dec.w["ones"], self.dec.eps), w, **kw)
+
+    def head(self, x, out):
+        return self._mm(ops.rmsnorm(x, self.dec.w["norm_w"], self.dec.eps), self.lm_head, out_f32=True, out=out)
+
+
+class _Gemv(_Form):
+    """GEMV with the RMSNorm fused into the kernel (fp8: plain RMS, the weight folded in), one row or a few (batched: one pass over the
+    weights for all rows, each bit for bit the single-row call)."""
+
+    def __init__(self, dec, fp8, batched):
+        super().__init__(dec, fp8)
+        self._mv = (ops.gemv_batched_fp8 if batched else ops.gemv_fp8) if fp8 else (ops.gemv_batched if batched else ops.gemv)
+
+    def _mm(self, a, w, **kw):
+        return self._mv(*w, a, **kw) if self.fp8 else self._mv(w, a, **kw)
+
+    def normed(self, x, w, **kw):
+        fold = dict(rms_plain=True) if self.fp8 else dict(norm_w=self.dec.w["ones"])
+        return self._mm(x, w, eps=self.dec.eps, **fold, **kw)
+
+    def head(self, x, out):
+        return self._mm(x, self.lm_head, norm_w=self.dec.w["norm_w"], eps=self.dec.eps, out_f32=True, out=out)
+
+
 class HipMistralDecoder(nn.Module):
     """tp_group: optional torch.distributed group for tensor parallelism over the heads / MLP width (the
     reference has none -- its 72B path is accelerate's device_map="auto").  Every rank holds 1/tp of the q/k/v/gate/up rows
@@ -67,6 +166,7 @@ class HipMistralDecoder(nn.Module):
         # validation hook for 1-GPU boxes: issue the tensor-parallel all-reduces even when the group has ONE rank (the sum over one
         # rank is the identity), so that the captured-RCCL decode graph can be exercised on hardware without a second GPU
         self.tp_always_reduce = False
+        self.decode_fp8 = self.prefill_fp8 = False
 
     @torch.no_grad()
     def enable_fp8_decode(self, on=True):
@@ -139,19 +239,39 @@ class HipMistralDecoder(nn.Module):
                 dist.all_reduce(t, group=self.tp_group)
         return t
 
-    def _row_parallel(self, a, w, x, rs, rn):
-        """x + a @ w.T (o_proj / down_proj with the residual fused); leaves (0, rstd) of the result's rows in `rn` for the next
-        norm-carrying GEMM.  Single rank: the GEMM's epilogue emits the partial statistics (`rs`).  Tensor parallel: the GEMM output
-        is a partial sum, so the statistics are taken after the all-reduce (one extra read of x)."""
-        if self.tp > 1:
-            x = self._reduce(ops.gemm(a, w, res=x if self.tp_rank == 0 else None))
-            ops.row_stats(x, out=rs)
-        else:
-            x = ops.gemm(a, w, res=x, stats_out=rs)
-        ops.row_norm_finalize(rs, self.D, ops.NORM_RMS, self.eps, out=rn)
+    # ------------------------------------------------------------------ the rows loop: prefill, prefill_batch, extend (MFMA GEMMs)
+    def _rows(self, f, x, segs, outs, append=False):
+        """One pass of the layers over the rows x [n, D] with projection form f.  segs = [(s0, s1, P, k per layer, v per layer)]: rows
+        s0 .. s1-1 are the positions P .. P + s1 - s0 - 1 of the sequence that owns those caches.  The projections run on all rows at once;
+        RoPE, the cache write and the causal attention run per segment on its own cache (append: vl2_attn_append; otherwise vl2_attn_fwd
+        with causal_off).  Every form ends on the 16-bit lm_head: the fp32 logits of each segment's last row go to its entry of `outs`.
+        Returns the last hidden state [n, D]."""
+        nh, nkv, hd, smax = self.nh, self.nkv, self.hd, self.max_seq_len
+        q = torch.empty((x.shape[0], nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
+        o = torch.empty_like(q)
+        f.begin(x)
+        for li, lw in enumerate(self.w["layers"]):
+            qkv = f.normed(x, f.layers[li]["wqkv"], bias=lw["bqkv"])          # bqkv: Qwen2 only
+            for s0, s1, P, kc, vc in segs:
+                n = s1 - s0
+                ops.rope_kv(qkv[s0:s1], q[s0:s1], kc[li], vc[li], self.cos_t, self.sin_t, nh, nkv, P)
+                if append:
+                    ops.attn_append(q[s0:s1], kc[li], vc[li], o[s0:s1], P, nh, nkv, hd ** -0.5)
+                else:
+                    ops.attn_fwd(q[s0:s1], kc[li], vc[li], o[s0:s1], (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
+                                 (0, hd, nh * hd), 1, nh, n, P + n, nh // nkv, hd ** -0.5, True, P, hd)
+            x = self._rows_block(f, li, o, x)
+        for (_, s1, _, _, _), out in zip(segs, outs):
+            ops.gemv(self.w["lm_head"], x[s1 - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=out)
         return x
 
-    # ------------------------------------------------------------------ prefill (M = S tokens, MFMA GEMMs)
+    def _rows_block(self, f, li, o, x):
+        """The rest of a layer after attention, many rows: x + o_proj(o), then the MLP (SwiGLU) with its residual.
+        (HipMixtralDecoder replaces it by its sparse MoE block.)"""
+        wl = f.layers[li]
+        x = f.res(o, wl["wo"], x)
+        return f.res(f.normed(x, wl["wgu"], swiglu=True), wl["wd"], x)
+
     @torch.no_grad()
     def prefill(self, x, return_all_logits=False, cache=None, logits_out=None):
         """x: inputs_embeds [S, D] (any float dtype, device).  Fills the KV cache for positions 0..S-1 and returns
@@ -165,53 +285,21 @@ class HipMistralDecoder(nn.Module):
         x = x.to(device=self._dev, dtype=_lib.elem_dtype()).contiguous()
         if cache is None:
             self.cache_epoch += 1
+        out = self.logits if logits_out is None else logits_out
         if self._use_stage(cache) and not return_all_logits:      # the whole prefill as one call into libvl2hip.so (vl2_llm_prefill)
-            out = self.logits if logits_out is None else logits_out
-            ops.llm_prefill(self._stage_desc()[0], x, out, fp8=getattr(self, "prefill_fp8", False))
+            ops.llm_prefill(self._stage_desc()[0], x, out, fp8=self.prefill_fp8)
             self.pos = S
             self.last_hidden = None
             return out
-        nh, nkv, hd, D = self.nh, self.nkv, self.hd, self.D
-        q = torch.empty((S, nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
-        o = torch.empty((S, nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
-        smax = self.max_seq_len
-        if getattr(self, "prefill_fp8", False):                   # the same pass operator by operator on the fp8 matrix pipe (vl2_stage.inc)
-            for li, (lw, w8) in enumerate(zip(self.w["layers"], self.w8["layers"])):
-                a8, tab = ops.quant_act_fp8(x, rms_eps=self.eps)
-                qkv = ops.gemm_fp8(a8, tab, *w8["wqkv"], bias=lw["bqkv"])
-                ops.rope_kv(qkv, q, kcache[li], vcache[li], self.cos_t, self.sin_t, nh, nkv, 0)
-                ops.attn_fwd(q, kcache[li], vcache[li], o, (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
-                             (0, hd, nh * hd), 1, nh, S, S, nh // nkv, hd ** -0.5, True, 0, hd)
-                a8, tab = ops.quant_act_fp8(o)
-                x1 = ops.gemm_fp8(a8, tab, *w8["wo"], res=x)
-                a8, tab = ops.quant_act_fp8(x1, rms_eps=self.eps)
-                a = ops.gemm_fp8(a8, tab, *w8["wgu"], swiglu=True)
-                a8, tab = ops.quant_act_fp8(a)
-                x = ops.gemm_fp8(a8, tab, *w8["wd"], res=x1)
-            self.pos = S
-            self.last_hidden = x
-            if return_all_logits:
-                h = ops.rmsnorm(x, self.w["norm_w"], self.eps)
-                return ops.gemm(h, self.w["lm_head"], out_f32=True)
-            return ops.gemv(self.w["lm_head"], x[S - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True,
-                            out=self.logits if logits_out is None else logits_out)
-        rs = ops.row_stats(x)          # RMSNorm rides in the q/k/v and gate/up GEMMs (weights.fold_norm): this seeds the statistics
-        rn = ops.row_norm_finalize(rs, D, ops.NORM_RMS, self.eps)       # [S, 2] (0, rstd): reduced once, not in every column tile
-        for li, lw in enumerate(self.w["layers"]):
-            qkv = ops.gemm(x, lw["wqkv"], bias=lw["bqkv"], norm=(ops.NORM_RMS, rn, self.eps, None))   # bqkv: Qwen2 only
-            ops.rope_kv(qkv, q, kcache[li], vcache[li], self.cos_t, self.sin_t, nh, nkv, 0)
-            ops.attn_fwd(q, kcache[li], vcache[li], o, (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
-                         (0, hd, nh * hd), 1, nh, S, S, nh // nkv, hd ** -0.5, True, 0, hd)
-            x = self._prefill_block_out(lw, o, x, rs, rn)
+        # operator by operator: the RMSNorm rides in the q/k/v and gate/up GEMMs (weights.fold_norm), or the fp8 matrix pipe (vl2_stage.inc)
+        f = _W8A8(self) if self.prefill_fp8 else _Tiled(self)
+        x = self._rows(f, x, [(0, S, 0, kcache, vcache)], () if return_all_logits else (out,))
         self.pos = S
         self.last_hidden = x
         if return_all_logits:
-            h = ops.rmsnorm(x, self.w["norm_w"], self.eps)
-            return ops.gemm(h, self.w["lm_head"], out_f32=True)
-        return ops.gemv(self.w["lm_head"], x[S - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True,
-                        out=self.logits if logits_out is None else logits_out)
+            return ops.gemm(ops.rmsnorm(x, self.w["norm_w"], self.eps), self.w["lm_head"], out_f32=True)
+        return out
 
-    # ------------------------------------------------------------------ extend (prefill of new rows on top of the resident cache)
     EXTEND_SKINNY_ROWS = 64      # up to this many rows the projections stream the weights once on the skinny-M kernel (ops.gemm_skinny)
     EXTEND_APPEND_ROWS = 64      # up to this many rows the attention is vl2_attn_append (split-KV); beyond, vl2_attn_fwd with causal_off
 
@@ -220,12 +308,12 @@ class HipMistralDecoder(nn.Module):
         """Prefill of the rows start_pos .. start_pos + n - 1 (default start_pos = self.pos) against the single-sequence KV cache, whose
         rows 0 .. start_pos - 1 must already hold the sequence (a previous prefill / extend / decode steps); rows from start_pos on are
         overwritten.  x_new: inputs_embeds [n, D].  Leaves the last row's fp32 logits in self.logits (returned) and self.pos =
-        start_pos + n.  Per layer: q/k/v projection, RoPE + cache append at start_pos (ops.rope_kv), append attention
-        (ops.attn_append), then the family's `_extend_block_out` (Mixtral: its MoE block with S = n)."""
+        start_pos + n.  Few rows: the skinny-M projections (RMSNorm as its own launch, like the batched decode step) and the append
+        attention; otherwise the prefill's tiled GEMMs and vl2_attn_fwd."""
         _lib.check_elem(self._elem, type(self).__name__)
         if self.tp > 1 or self.tp_always_reduce:
             raise NotImplementedError("extend: single-rank decoders only")
-        if getattr(self, "prefill_fp8", False):
+        if self.prefill_fp8:
             raise NotImplementedError("extend runs the 16-bit projections: call enable_fp8_prefill(False) first")
         P = self.pos if start_pos is None else int(start_pos)
         n = x_new.shape[0]
@@ -237,79 +325,43 @@ class HipMistralDecoder(nn.Module):
             raise ValueError(f"sequence length {P + n} exceeds the KV cache ({self.max_seq_len})")
         self.cache_epoch += 1
         x = x_new.to(device=self._dev, dtype=_lib.elem_dtype()).contiguous()
-        nh, nkv, hd, smax = self.nh, self.nkv, self.hd, self.max_seq_len
-        q = torch.empty((n, nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
-        o = torch.empty((n, nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
-        skinny = n <= self.EXTEND_SKINNY_ROWS
-        rs = ops.row_stats(x)
-        rn = ops.row_norm_finalize(rs, self.D, ops.NORM_RMS, self.eps)
-        for li, lw in enumerate(self.w["layers"]):
-            if skinny:
-                qkv = ops.gemm_skinny(ops.rmsnorm(x, self.w["ones"], self.eps), lw["wqkv"], bias=lw["bqkv"])
-            else:
-                qkv = ops.gemm(x, lw["wqkv"], bias=lw["bqkv"], norm=(ops.NORM_RMS, rn, self.eps, None))
-            ops.rope_kv(qkv, q, self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, nh, nkv, P)
-            if n <= self.EXTEND_APPEND_ROWS:
-                ops.attn_append(q, self.kcache[li], self.vcache[li], o, P, nh, nkv, hd ** -0.5)
-            else:
-                ops.attn_fwd(q, self.kcache[li], self.vcache[li], o, (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
-                             (0, hd, nh * hd), 1, nh, n, P + n, nh // nkv, hd ** -0.5, True, P, hd)
-            x = self._extend_block_out(lw, o, x, rs, rn, skinny)
+        f = _Skinny(self, False, n) if n <= self.EXTEND_SKINNY_ROWS else _Tiled(self)
+        out = self.logits if logits_out is None else logits_out
+        x = self._rows(f, x, [(0, n, P, self.kcache, self.vcache)], (out,), append=n <= self.EXTEND_APPEND_ROWS)
         self.pos = P + n
         self.last_hidden = x
-        return ops.gemv(self.w["lm_head"], x[n - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True,
-                        out=self.logits if logits_out is None else logits_out)
+        return out
 
-    def _extend_block_out(self, lw, o, x, rs, rn, skinny):
-        """The rest of an extend layer after attention.  Few rows: o_proj, gate/up and down on the skinny-M kernel (RMSNorm as its own
-        launch, like the batched decode step); otherwise the prefill's tiled GEMMs (`_prefill_block_out`, which also leaves rn)."""
-        if not skinny:
-            return self._prefill_block_out(lw, o, x, rs, rn)
-        x1 = ops.gemm_skinny(o, lw["wo"], res=x)
-        a = ops.gemm_skinny(ops.rmsnorm(x1, self.w["ones"], self.eps), lw["wgu"], swiglu=True)
-        return ops.gemm_skinny(a, lw["wd"], res=x1)
+    # ------------------------------------------------------------------ the token loop: decode steps (M = 1 or the batch, HBM-bound)
+    def _tokens(self, f, attend, x, x1, qkv, o, a, logits):
+        """One decode step's layers over x ([D], or [nb, D] for the batch) with projection form f, on the step's buffers x1 / qkv / o / a.
+        attend(li, qkv, o): RoPE + cache append + attention on layer li's cache.  Leaves the fp32 logits in `logits`."""
+        for li, lw in enumerate(self.w["layers"]):
+            f.normed(x, f.layers[li]["wqkv"], bias=lw["bqkv"], out=qkv)
+            attend(li, qkv, o)
+            self._token_block(f, li, o, x, x1, a)
+        f.head(x, logits)
 
-    def _prefill_block_out(self, lw, o, x, rs, rn):
-        """The rest of a prefill layer after attention: x + o_proj(o), then the MLP (SwiGLU) with its residual; leaves (0, rstd) of
-        the result in `rn` for the next layer's q/k/v GEMM.  (HipMixtralDecoder replaces the MLP by its sparse MoE block.)"""
-        x = self._row_parallel(o, lw["wo"], x, rs, rn)
-        a = ops.gemm(x, lw["wgu"], swiglu=True, norm=(ops.NORM_RMS, rn, self.eps, None), mfma16=True)
-        return self._row_parallel(a, lw["wd"], x, rs, rn)
+    def _token_block(self, f, li, o, x, x1, a):
+        """The rest of a decode layer after attention: x1 = x + o_proj(o), then x = x1 + MLP(x1) in place (x's old value is dead).
+        (HipMixtralDecoder replaces the MLP by its sparse MoE GEMVs.)"""
+        wl = f.layers[li]
+        f.res(o, wl["wo"], x, out=x1)
+        f.res(f.normed(x1, wl["wgu"], swiglu=True, out=a), wl["wd"], x1, out=x)
 
-    # ------------------------------------------------------------------ decode (M = 1, HBM-bound GEMVs)
     def _decode_kernels(self, dyn):
         """Enqueue one decode step for the token in self.tok: embed -> 32 x {qkv GEMV (+RMSNorm), RoPE+append+attention,
-        o GEMV (+res), gate/up GEMV (+RMSNorm, SwiGLU), down GEMV (+res)} -> lm_head GEMV (+final RMSNorm) into self.logits.
-        dyn=True reads the position from self.state[0] on the device (hipGraph-replayable); no allocation either way."""
-        b, nh, nkv, hd = self._b, self.nh, self.nkv, self.hd
+        o GEMV (+res), gate/up GEMV (+RMSNorm, SwiGLU), down GEMV (+res)} -> lm_head GEMV (+final RMSNorm) into self.logits, on the
+        16-bit weights or their fp8 copies (enable_fp8_decode).  dyn=True reads the position from self.state[0] on the device
+        (hipGraph-replayable); no allocation either way."""
+        b = self._b
         pos_dev = self.state[0:1] if dyn else None
         ops.embed_rows(self.tok, self.w["embed"], b["x0"])
-        x = b["x0"][0]
-        if getattr(self, "decode_fp8", False):                  # the same step on the fp8 copies (vl2_gemv_fp8), operator by operator
-            for li, (lw, q) in enumerate(zip(self.w["layers"], self.w8["layers"])):
-                ops.gemv_fp8(*q["wqkv"], x, eps=self.eps, out=b["qkv"], bias=lw["bqkv"], rms_plain=True)
-                ops.attn_decode(b["qkv"], self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, self.partial, b["o"], nh, nkv,
-                                self.pos, hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
-                ops.gemv_fp8(*q["wo"], b["o"], res=x, out=b["x1"])
-                ops.gemv_fp8(*q["wgu"], b["x1"], eps=self.eps, swiglu=True, out=b["a"], rms_plain=True)
-                ops.gemv_fp8(*q["wd"], b["a"], res=b["x1"], out=x)
-            ops.gemv_fp8(*self.w8["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=self.logits)
-            return
-        for li, lw in enumerate(self.w["layers"]):
-            ops.gemv(lw["wqkv"], x, norm_w=self.w["ones"], eps=self.eps, out=b["qkv"], bias=lw["bqkv"])   # ln weight folded into wqkv
-            ops.attn_decode(b["qkv"], self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, self.partial, b["o"], nh, nkv,
-                            self.pos, hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
-            self._decode_block_out(lw, x)
-        ops.gemv(self.w["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=self.logits)
 
-    def _decode_block_out(self, lw, x):
-        """The rest of a decode layer after attention (o in self._b["o"]): x1 = x + o_proj(o), then x = x1 + MLP(x1) in place.
-        (HipMixtralDecoder replaces the MLP by its sparse MoE GEMVs.)"""
-        b = self._b
-        r0 = self.tp_rank == 0                                              # the residual rides on rank 0's partial sum
-        self._reduce(ops.gemv(lw["wo"], b["o"], res=x if r0 else None, out=b["x1"]))          # x1 = x + attn
-        ops.gemv(lw["wgu"], b["x1"], norm_w=self.w["ones"], eps=self.eps, swiglu=True, out=b["a"])
-        self._reduce(ops.gemv(lw["wd"], b["a"], res=b["x1"] if r0 else None, out=x))          # x = x1 + mlp (x's old value is dead)
+        def attend(li, qkv, o):
+            ops.attn_decode(qkv, self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, self.partial, o, self.nh, self.nkv,
+                            self.pos, self.hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
+        self._tokens(_Gemv(self, self.decode_fp8, batched=False), attend, b["x0"][0], b["x1"], b["qkv"], b["o"], b["a"], self.logits)
 
     @torch.no_grad()
     def decode_step(self, tok_dev=None):
@@ -337,34 +389,45 @@ class HipMistralDecoder(nn.Module):
             return self.graph
         if sampler is not None and getattr(self, "_graph_sample", (None, None))[0] == tuple(sampler):
             return self._graph_sample[1]
-        saved = (self.state.clone(), self.tok.clone(), self.logits.clone(), self.hist[:2].clone())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
         def one_step():                                       # argmax + the token's forward: ONE call into libvl2hip.so
             if sampler is not None:                           # (the stage call opens with its own argmax: the sampled step is the operator sequence)
                 ops.sample_token(self.logits, self.tok, self.u_buf, sampler[0], sampler[1], sampler[2], hist=self.hist, state=self.state)
                 self._decode_kernels(dyn=True)
             elif self._use_stage():
                 d, _, ws = self._stage_desc()
-                ops.llm_decode_step(d, self.logits, self.tok, self.state, self.hist, self.partial, ws, fp8=getattr(self, "decode_fp8", False))
+                ops.llm_decode_step(d, self.logits, self.tok, self.state, self.hist, self.partial, ws, fp8=self.decode_fp8)
             else:
                 ops.argmax(self.logits, self.tok, self.hist, 0, self.state)
                 self._decode_kernels(dyn=True)
 
-        with torch.cuda.stream(side):                       # warm-up outside capture (first-launch attribute calls etc.)
+        def warm_up():
             self.state.copy_(torch.tensor([max(self.pos - 1, 0), 0], dtype=torch.int32))
             one_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):   # a RCCL watchdog thread may be polling events
-            one_step()
-        self.state.copy_(saved[0]); self.tok.copy_(saved[1]); self.logits.copy_(saved[2]); self.hist[:2].copy_(saved[3])
-        torch.cuda.synchronize()
+        g = self._capture(warm_up, one_step, (self.state, self.tok, self.logits, self.hist[:2]))
         if sampler is not None:
             self._graph_sample = (tuple(sampler), g)
         else:
             self.graph = g
+        return g
+
+    @staticmethod
+    def _capture(warm_up, step, keep):
+        """`step` as a hipGraph: warm-up outside capture on a side stream (first-launch attribute calls, the allocator), capture in
+        thread-local mode (a RCCL watchdog thread may be polling events), then the tensors in `keep`, which the warm-up advanced, are
+        restored."""
+        saved = [t.clone() for t in keep]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm_up()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            step()
+        for t, s in zip(keep, saved):
+            t.copy_(s)
+        torch.cuda.synchronize()
         return g
 
     @torch.no_grad()
@@ -381,9 +444,7 @@ class HipMistralDecoder(nn.Module):
         given one), so `torch.manual_seed` makes a run repeatable like it does for the reference.
         start_pos: None = prefill `inputs_embeds` from position 0 (the plain path); an int = the cache already holds the sequence's rows
         0 .. start_pos - 1 and `inputs_embeds` are its rows from start_pos on (`extend`), then the same decode loop."""
-        eos = set()
-        if eos_token_id is not None:
-            eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
+        eos = eos_set(eos_token_id)
         if start_pos is None:
             logits = self.prefill(inputs_embeds)
         else:
@@ -444,7 +505,7 @@ class HipMistralDecoder(nn.Module):
         M: fuller GEMM grids), RoPE / cache fill / causal attention per sequence on its own cache.  Every kernel here is
         row-independent, so the result is bit-identical to prefilling the prompts one by one.
         xs: list of [S_b, D]; caches: list of (k per layer, v per layer); logits_out: [B, V] fp32 (last position of each)."""
-        if getattr(self, "prefill_fp8", False):
+        if self.prefill_fp8:
             raise NotImplementedError("fp8 prefill (enable_fp8_prefill) covers the single-sequence prefill; the batched prefill runs the 16-bit "
                                       "projections: call enable_fp8_prefill(False) first")
         lens = [x.shape[0] for x in xs]
@@ -453,26 +514,11 @@ class HipMistralDecoder(nn.Module):
         if any(len(kc) and kc[0] is self.kcache[0] for kc, _ in caches):
             self.cache_epoch += 1
         X = torch.cat([x.to(device=self._dev, dtype=_lib.elem_dtype()) for x in xs], 0).contiguous()
-        offs = [0]
-        for n in lens:
-            offs.append(offs[-1] + n)
-        nh, nkv, hd, smax = self.nh, self.nkv, self.hd, self.max_seq_len
-        q = torch.empty((offs[-1], nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
-        o = torch.empty((offs[-1], nh * hd), dtype=_lib.elem_dtype(), device=self._dev)
-        rs = ops.row_stats(X)
-        rn = ops.row_norm_finalize(rs, self.D, ops.NORM_RMS, self.eps)
-        for li, lw in enumerate(self.w["layers"]):
-            qkv = ops.gemm(X, lw["wqkv"], bias=lw["bqkv"], norm=(ops.NORM_RMS, rn, self.eps, None))
-            for b, (kc, vc) in enumerate(caches):
-                s0, s1, S = offs[b], offs[b + 1], lens[b]
-                ops.rope_kv(qkv[s0:s1], q[s0:s1], kc[li], vc[li], self.cos_t, self.sin_t, nh, nkv, 0)
-                ops.attn_fwd(q[s0:s1], kc[li], vc[li], o[s0:s1], (0, hd, nh * hd), (0, smax * hd, hd), (0, smax * hd, hd),
-                             (0, hd, nh * hd), 1, nh, S, S, nh // nkv, hd ** -0.5, True, 0, hd)
-            X = self._row_parallel(o, lw["wo"], X, rs, rn)
-            a = ops.gemm(X, lw["wgu"], swiglu=True, norm=(ops.NORM_RMS, rn, self.eps, None), mfma16=True)
-            X = self._row_parallel(a, lw["wd"], X, rs, rn)
-        for b in range(len(xs)):
-            ops.gemv(self.w["lm_head"], X[offs[b + 1] - 1], norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=logits_out[b])
+        segs, s0 = [], 0
+        for n, (kc, vc) in zip(lens, caches):
+            segs.append((s0, s0 + n, 0, kc, vc))
+            s0 += n
+        self._rows(_Tiled(self), X, segs, logits_out)
         return lens
 
     def _ensure_batch(self, B, owner=None):
@@ -519,88 +565,21 @@ class HipMistralDecoder(nn.Module):
         With enable_fp8_decode the same step streams the fp8 copies (W8A16): the multi-row fp8 GEMV below GEMM_BATCH (a row is bit-identical
         to the single-sequence fp8 step), the fp8 skinny-M kernel from GEMM_BATCH on, in calls of at most 64 rows (bit-identical to the 16-bit
         skinny-M step on the dequantised weights)."""
-        bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
-        x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
+        bb = self._bb
+        x = bb["x0"][:nb]
         ops.embed_rows(bb["tok"][:nb], self.w["embed"], x)
-        r0 = self.tp_rank == 0
         if nb >= self.GEMM_BATCH:
-            # M = nb rows: every projection is a few-tile grid, i.e. bound by how many workgroups stream the weights; split-K
-            # (partials through the workspace) is wired but off, see SPLITK_IN_BATCHED_GEMM.
-            ops.set_splitk(self.SPLITK_IN_BATCHED_GEMM and self._dev.type == "cuda")
-            try:
-                self._batched_gemm_step(nb)
-            finally:
-                ops.set_splitk(False)
-            return
-        self._batched_gemv_step(nb)
+            # M = nb rows: every projection is a few-tile grid, bound by how many workgroups stream the weights.  Split-K (partials
+            # through the workspace) measured no gain here (B=16 8.09 vs 8.01 ms per step): the fp32 partial exchange costs what it saves
+            ops.set_splitk(False)
+            f = _Skinny(self, self.decode_fp8, nb)
+        else:
+            f = _Gemv(self, self.decode_fp8, batched=True)
 
-    SPLITK_IN_BATCHED_GEMM = False      # measured: no gain (B=16 8.09 vs 8.01 ms per step): the fp32 partial exchange costs what it saves
-
-    def _batched_gemm_step(self, nb):
-        bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
-        x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
-        r0 = self.tp_rank == 0
-        if getattr(self, "decode_fp8", False):
-            self._batched_gemm_step_fp8(nb)
-            return
-        # up to 64 rows: the skinny-M kernel streams the weights GEMV-style into MFMA; beyond that the tiled GEMMs
-        mm = ops.gemm_skinny if nb <= 64 else ops.gemm
-        for li, lw in enumerate(self.w["layers"]):
-            h = ops.rmsnorm(x, self.w["ones"], self.eps)                  # the norm weights are folded into wqkv / wgu
-            mm(h, lw["wqkv"], bias=lw["bqkv"], out=qkv)
-            ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
-                                    bb["pos"][:nb], self.max_seq_len, hd ** -0.5)
-            self._reduce(mm(o, lw["wo"], res=x if r0 else None, out=x1))
-            h = ops.rmsnorm(x1, self.w["ones"], self.eps)
-            mm(h, lw["wgu"], swiglu=True, out=a)
-            self._reduce(mm(a, lw["wd"], res=x1 if r0 else None, out=x))
-        h = ops.rmsnorm(x, self.w["norm_w"], self.eps)
-        mm(h, self.w["lm_head"], out_f32=True, out=bb["logits"][:nb])
-        bb["pos"][:nb] += 1
-
-    def _batched_gemm_step_fp8(self, nb):
-        """_batched_gemm_step on the fp8 copies: the skinny-M fp8 kernel for every projection and any nb (ops.gemm_skinny_fp8 runs more
-        than 64 rows in calls of at most 64, the weights streamed once per call); norms, bias and residual wiring as the 16-bit step.
-        (fp8 decode weights are single-rank: no all-reduce.)"""
-        bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
-        x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
-        for li, (lw, q) in enumerate(zip(self.w["layers"], self.w8["layers"])):
-            h = ops.rmsnorm(x, self.w["ones"], self.eps)                  # the norm weights are folded into wqkv / wgu (and their fp8 copies)
-            ops.gemm_skinny_fp8(h, *q["wqkv"], bias=lw["bqkv"], out=qkv)
-            ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
-                                    bb["pos"][:nb], self.max_seq_len, hd ** -0.5)
-            ops.gemm_skinny_fp8(o, *q["wo"], res=x, out=x1)
-            h = ops.rmsnorm(x1, self.w["ones"], self.eps)
-            ops.gemm_skinny_fp8(h, *q["wgu"], swiglu=True, out=a)
-            ops.gemm_skinny_fp8(a, *q["wd"], res=x1, out=x)
-        h = ops.rmsnorm(x, self.w["norm_w"], self.eps)
-        ops.gemm_skinny_fp8(h, *self.w8["lm_head"], out_f32=True, out=bb["logits"][:nb])
-        bb["pos"][:nb] += 1
-
-    def _batched_gemv_step(self, nb):
-        bb, nh, nkv, hd = self._bb, self.nh, self.nkv, self.hd
-        x, x1, qkv, o, a = bb["x0"][:nb], bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb]
-        r0 = self.tp_rank == 0
-        if getattr(self, "decode_fp8", False):
-            # the single-sequence fp8 step (_decode_kernels) row by row: q/k/v and gate/up RMS-normalise x without a weight (folded into W)
-            for li, (lw, q) in enumerate(zip(self.w["layers"], self.w8["layers"])):
-                ops.gemv_batched_fp8(*q["wqkv"], x, eps=self.eps, out=qkv, bias=lw["bqkv"], rms_plain=True)
-                ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
-                                        bb["pos"][:nb], self.max_seq_len, hd ** -0.5)
-                ops.gemv_batched_fp8(*q["wo"], o, res=x, out=x1)
-                ops.gemv_batched_fp8(*q["wgu"], x1, eps=self.eps, swiglu=True, out=a, rms_plain=True)
-                ops.gemv_batched_fp8(*q["wd"], a, res=x1, out=x)
-            ops.gemv_batched_fp8(*self.w8["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=bb["logits"][:nb])
-            bb["pos"][:nb] += 1
-            return
-        for li, lw in enumerate(self.w["layers"]):
-            ops.gemv_batched(lw["wqkv"], x, norm_w=self.w["ones"], eps=self.eps, out=qkv, bias=lw["bqkv"])
-            ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, nh, nkv,
-                                    bb["pos"][:nb], self.max_seq_len, hd ** -0.5)
-            self._reduce(ops.gemv_batched(lw["wo"], o, res=x if r0 else None, out=x1))
-            ops.gemv_batched(lw["wgu"], x1, norm_w=self.w["ones"], eps=self.eps, swiglu=True, out=a)
-            self._reduce(ops.gemv_batched(lw["wd"], a, res=x1 if r0 else None, out=x))
-        ops.gemv_batched(self.w["lm_head"], x, norm_w=self.w["norm_w"], eps=self.eps, out_f32=True, out=bb["logits"][:nb])
+        def attend(li, qkv, o):
+            ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, self.nh, self.nkv,
+                                    bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
+        self._tokens(f, attend, x, bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb], bb["logits"][:nb])
         bb["pos"][:nb] += 1
 
     def _sample_rows(self, nb):
@@ -631,20 +610,8 @@ class HipMistralDecoder(nn.Module):
         if self.tp > 1:
             raise NotImplementedError("hipGraph decode is built for the single-GPU decoder (collectives are launched eagerly)")
         bb = self._bb
-        saved = (bb["tok"].clone(), bb["pos"].clone(), bb["logits"].clone(), bb["sstep"].clone())
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                       # warm-up outside capture (first-launch attribute calls, allocator)
-            self._batched_step(nb, sampled)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        bb["pos"].copy_(saved[1]); bb["sstep"].copy_(saved[3])
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._batched_step(nb, sampled)
-        bb["tok"].copy_(saved[0]); bb["pos"].copy_(saved[1]); bb["logits"].copy_(saved[2]); bb["sstep"].copy_(saved[3])
-        torch.cuda.synchronize()
-        graphs[key] = g
+        step = lambda: self._batched_step(nb, sampled)
+        graphs[key] = g = self._capture(step, step, (bb["tok"], bb["pos"], bb["logits"], bb["sstep"]))
         return g
 
     @torch.no_grad()
@@ -670,9 +637,7 @@ class HipMistralDecoder(nn.Module):
             gen = sampler[3] if len(sampler) > 3 else None
             n_u = min(max_new_tokens, self.max_seq_len) + 1
             u_rows = torch.stack([torch.rand((n_u,), device=self._dev, generator=gen) for _ in range(nb)]).contiguous()
-        eos = set()
-        if eos_token_id is not None:
-            eos = set(eos_token_id) if isinstance(eos_token_id, (list, tuple, set)) else {int(eos_token_id)}
+        eos = eos_set(eos_token_id)
         bb = self._ensure_batch(nb)
         sampled = sampler is not None
         if sampled:
@@ -782,22 +747,20 @@ class HipMixtralDecoder(HipMistralDecoder):
             raise NotImplementedError("MoE (mixtral) decoder: external caches (batched decoding) not built")
         return super().prefill(x, return_all_logits=return_all_logits, logits_out=logits_out)
 
-    def _prefill_block_out(self, lw, o, x, rs, rn):
-        """x1 = x + o_proj(o) (its norm is taken by the router), then the sparse MoE block; the combine leaves (0, rstd) in `rn`."""
-        return self.moe_block(lw, ops.gemm(o, lw["wo"], res=x), rn)
+    def _rows_block(self, f, li, o, x):
+        """x1 = x + o_proj(o) on the tiled GEMM whatever the form (its norm is taken by the router), then the sparse MoE block (any row
+        count); the combine leaves (0, rstd) in the form's rn."""
+        lw = self.w["layers"][li]
+        return self.moe_block(lw, ops.gemm(o, lw["wo"], res=x), f.rn)
 
-    def _extend_block_out(self, lw, o, x, rs, rn, skinny):
-        """The MoE block of the prefill with S = n rows (the router, grouping and grouped GEMMs take any row count)."""
-        return self._prefill_block_out(lw, o, x, rs, rn)
-
-    def _decode_block_out(self, lw, x):
+    def _token_block(self, f, li, o, x, x1, a):
         """x1 = x + o_proj(o); router GEMV (+RMSNorm, softmax, top-k -> ids / weights on the device); gate/up+SwiGLU GEMV of the k chosen
         experts (one launch); down GEMV of both (one launch, weighted, + residual) into x.  No host read: the step replays as a graph."""
-        b = self._b
-        ops.gemv(lw["wo"], b["o"], res=x, out=b["x1"])
-        ops.moe_route_gemv(b["x1"], lw["wr"], self.moe_ids, self.moe_wts, self.eps)
-        ops.moe_gemv(lw["wgu"], b["x1"], self.moe_ids, swiglu=True, eps=self.eps, out=b["a"])
-        ops.moe_gemv(lw["wd"], b["a"], self.moe_ids, wts=self.moe_wts, res=b["x1"], out=x)
+        lw = self.w["layers"][li]
+        ops.gemv(lw["wo"], o, res=x, out=x1)
+        ops.moe_route_gemv(x1, lw["wr"], self.moe_ids, self.moe_wts, self.eps)
+        ops.moe_gemv(lw["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
+        ops.moe_gemv(lw["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
 
 
 def make_decoder(cfg, *args, **kwargs):

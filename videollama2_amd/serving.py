@@ -17,6 +17,8 @@ import itertools
 
 import torch
 
+from .decoder import eos_set
+
 
 class _Request:
     __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done", "sampler", "u")
@@ -40,8 +42,7 @@ class ContinuousBatcher:
             raise NotImplementedError("continuous batching is built for the single-GPU decoder")
         self.dec = decoder
         self.max_slots = int(max_slots)
-        eos = eos_token_id
-        self.eos = set() if eos is None else (set(eos) if isinstance(eos, (list, tuple, set)) else {int(eos)})
+        self.eos = eos_set(eos_token_id)
         self.use_graph = (decoder._dev.type == "cuda") if use_graph is None else bool(use_graph)
         self.waiting = collections.deque()
         self.slots = [None] * self.max_slots
