@@ -280,6 +280,28 @@ int32_t vl2_gemm_skinny_fp8(const void* A, const void* q, const float* scale, vo
 int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
                              int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps, int32_t flags,
                              void* stream);
+/* ---- MXFP4 weights for decode (csrc/k_mxfp4.h; additions of ABI 7).  OCP Microscaling Formats v1.0: E2M1 elements (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6},
+ * code bits s e e m) with ONE E8M0 power-of-two scale per block of 32 consecutive k: W[n][k] ~= 2^(s[n][k/32] - 127) * E2M1(q[n][k]); activations stay
+ * 16-bit (W4A16), fp32 sums.  q [N, ldq] bytes: byte j of a row = k = 2j in bits 3:0, k = 2j + 1 in bits 7:4; s [N, lds] bytes.  The reference has no
+ * such path: the quantiser IS the definition, restated in tests/mxfp4_oracle.py.  An OPTIONAL arithmetic, never a default.
+ * The pack call: w [N, ldw] 16-bit elements (K % 32 == 0) -> q [N, K / 2], s [N, lds]; per block e = floor(log2 max|w|) - 2 clamped to [-127, 127]
+ *   (0 for a zero block), code = round-to-nearest-even of w * 2^-e onto the E2M1 grid, saturating at +-6 (OCP MX v1.0 section 6.3).
+ * The one-token GEMV: y[N] = W~[N,K] x[K] (+ bias) (+ res) with norm_w / VL2_GEMV_RMS_PLAIN / VL2_GEMM_SWIGLU / VL2_GEMM_OUT_F32 as the fp8 GEMV
+ *   (SWIGLU: q and s in the packed 64-row block order).  N even, K % 32 == 0, K <= 32704, ldq % 16 == 0.
+ * The batched GEMV: MB rows in one pass over q per launch (up to 4 rows, as many as fit 64 KiB of LDS; larger MB is split); every row bit for bit
+ *   the one-token call.  ldx / ldy / ldres = element strides between rows.
+ * The skinny-M GEMM: C[M <= 64, N] = A W~^T (+bias | +res | SwiGLU | fp32 out) with the 16-bit skinny-M call's flags, checks and workspace; bit for bit
+ *   that call on the dequantised weights.  The K split depends on N and K only (a workspace too small for it is refused), so a row's result does not
+ *   depend on the other rows.  N % 64 == 0, K % 32 == 0. */
+int32_t vl2_pack_quant_mxfp4(const void* w, int64_t N, int64_t K, int64_t ldw, void* q, void* scale, int64_t lds, void* stream);
+int32_t vl2_gemv_mxfp4(const void* q, const void* scale, int32_t lds, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
+                       int32_t N, int32_t K, int32_t ldq, float eps, int32_t flags, void* stream);
+int32_t vl2_gemv_batched_mxfp4(const void* q, const void* scale, int32_t lds, const void* x, const float* norm_w, const void* res, const float* bias,
+                               void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps,
+                               int32_t flags, void* stream);
+int32_t vl2_gemm_skinny_mxfp4(const void* A, const void* q, const void* scale, int32_t lds, void* C, const float* bias, const void* res, int32_t M,
+                              int32_t N, int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws, int64_t ws_bytes,
+                              void* stream);
 /* Decode attention for ONE new token at position pos, fused with RoPE and the KV-cache append:
  *   qkv [(nh+2*nkv)*128] = un-roped fused q|k|v projection of the token; the kernel ropes q, ropes k and appends k,v to
  *   cache row pos (HF apply_rotary_pos_emb + DynamicCache.update), then softmax(q K^T / sqrt(d)) V over rows [0, pos]

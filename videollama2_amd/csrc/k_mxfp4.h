@@ -1,0 +1,329 @@
+// MXFP4 weights for the HBM-bound decode path: OCP Microscaling Formats v1.0 -- E2M1 elements (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, code bits
+// s e e m), ONE E8M0 power-of-two scale per block of 32 consecutive k of a weight row: W[n][k] ~= 2^e(n, k / 32) * E2M1(q[n][k]), 4.25 bits per
+// weight.  gfx950 reads the format natively: v_cvt_scalef32_pk_{bf16,f16}_fp4 turns one byte (two codes) and a scale into two 16-bit elements.
+// Like the fp8 copies (k_fp8.h) this is an OPTIONAL arithmetic of the decode step (W4A16: activations stay 16-bit, fp32 sums); the reference has
+// no such path, so the quantiser below IS the definition, restated in tests/mxfp4_oracle.py and held bit for bit against it.
+//
+// Storage: q [N, K / 2] bytes, byte j of a row = code of k = 2j in bits 3:0 and of k = 2j + 1 in bits 7:4 (the order the conversion instruction
+// reads: result[0] from the low nibble); s [N, K / 32] bytes = e + 127.
+//
+//   quant_mxfp4_rows_kernel  : per block, amax = max|w|, e = floor(log2 amax) - 2 (the exponent field of amax, no log) clamped to [-127, 127],
+//                              0 for a zero block; code = RNE of w * 2^-e onto the E2M1 grid, saturating at +-6 (OCP MX v1.0 section 6.3).
+//                              The scaling is exact and the rounding is seven comparisons: reproducible bit for bit on any machine.
+//   gemv_mxfp4_kernel        : y = W~ x for one token with gemv_fp8_kernel's prologue and epilogue (fused RMSNorm, SwiGLU pairing, bias,
+//                              residual, 16-bit / fp32 output).
+//   gemv_mr_mxfp4_kernel     : 2..4 rows of x in one pass over q, every row bit for bit the single-row kernel (ONE body, MB a parameter).
+//   gemm_skinny_mxfp4_kernel : M <= 64 rows on v_mfma_f32_16x16x32, the twin of gemm_skinny_fp8_kernel.
+//
+// THE SCALE RIDES IN THE CONVERSION in all of them: the element handed to v_dot2 / the MFMA is E2M1 * 2^e in the 16-bit element type.  bf16
+// holds that product exactly (one significant bit pair, fp32's exponent range); IEEE half holds it exactly while it stays inside half's range
+// (2^-24 .. 65504), which weights that were half to begin with do unless a block's maximum is below 2^-21.
+#pragma once
+#include "k_decode.h"
+#include "k_skinny.h"
+
+// byte B of dword w = two E2M1 codes -> two elements scaled by 2^(exponent of sc), packed like pack2bf (low nibble = low half)
+template <int B>
+__device__ __forceinline__ uint32_t mx4_cvt(uint32_t w, float sc) {
+#ifdef VL2_ELEM_F16
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, B));
+#else
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, B));
+#endif
+}
+// an E8M0 byte as the fp32 whose exponent field the conversion reads (byte 0 = 2^-127 is a fp32 denormal: written as one)
+__device__ __forceinline__ float mx4_scale(uint32_t sb) {
+    return __builtin_bit_cast(float, sb ? sb << 23 : 0x00400000u);
+}
+// 8 codes (k .. k+7, one dword) -> the 8 elements of an MFMA fragment / four dot2 operands, in order
+__device__ __forceinline__ u32x4 mx4_cvt8(uint32_t w, float sc) {
+    return u32x4{mx4_cvt<0>(w, sc), mx4_cvt<1>(w, sc), mx4_cvt<2>(w, sc), mx4_cvt<3>(w, sc)};
+}
+
+// |v| (already scaled by 2^-e) -> E2M1 magnitude code, round to nearest, ties to the even code, saturating at 6 (code 7)
+__device__ __forceinline__ uint32_t mx4_code(float v) {
+    const float a = fabsf(v);
+    const uint32_t c = a <= 0.25f ? 0u : a < 0.75f ? 1u : a <= 1.25f ? 2u : a < 1.75f ? 3u : a <= 2.5f ? 4u : a < 3.5f ? 5u : a <= 5.f ? 6u : 7u;
+    return c | ((__builtin_bit_cast(uint32_t, v) >> 28) & 8u);
+}
+
+// grid = N rows, block 256.  w [N, ldw] 16-bit elements, q [N, ldq] bytes, s [N, lds] bytes, K % 32 == 0.  A lane owns 8 consecutive k, four
+// lanes one block of 32.
+__global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const bf16_t* __restrict__ w, uint8_t* __restrict__ q, uint8_t* __restrict__ s,
+                                                               int K, long ldw, long ldq, long lds) {
+    const int tid = threadIdx.x;
+    const bf16_t* row = w + (size_t)blockIdx.x * ldw;
+    for (int k0 = 0; k0 < K; k0 += 2048) {               // uniform trip count: the four lanes of a block shuffle together
+        const int k = k0 + tid * 8;
+        const bool live = k < K;
+        float v[8];
+        unpack8(live ? *(const u32x4*)(row + k) : u32x4{0u, 0u, 0u, 0u}, v);
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+        amax = fmaxf(amax, __shfl_xor(amax, 1));
+        amax = fmaxf(amax, __shfl_xor(amax, 2));
+        // amax = 1.f * 2^x: floor(log2 amax) = x, the exponent field.  A denormal amax (only a bf16 denormal gets here) is below 2^-126:
+        // x - 2 < -127 clamps.  4 * 2^e <= amax < 8 * 2^e unless clamped.
+        const unsigned ab = __builtin_bit_cast(unsigned, amax);
+        const int E = (int)((ab >> 23) & 0xffu);
+        int e = E == 0 ? (ab ? -127 : 0) : E - 127 - 2;
+        e = e < -127 ? -127 : (e > 127 ? 127 : e);
+        const float inv = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);           // 2^-e: e = 127 -> 2^-127 cannot occur (amax < 2^128)
+        if (live) {
+            uint32_t o = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o |= mx4_code(v[j] * inv) << (4 * j);
+            *(uint32_t*)(q + (size_t)blockIdx.x * ldq + (k >> 1)) = o;
+            if ((tid & 3) == 0) s[(size_t)blockIdx.x * lds + (k >> 5)] = (uint8_t)(e + 127);
+        }
+    }
+}
+
+struct Gemv4Args {
+    const uint8_t* W;       // [N, ldw] bytes, two codes each (SWIGLU: packed blocks of 64 rows = 32 gate rows then 32 up rows, like the 16-bit layout)
+    const uint8_t* scale;   // [N, lds] E8M0 bytes, one per 32 k
+    const bf16_t* x;        // [K] (row 0 of [MB, ldx])
+    const float* norm_w;    // fused RMSNorm prologue on x (or null)
+    const bf16_t* res;      // [N_out] residual (or null)
+    void* y;                // 16-bit or fp32 [N_out]
+    int N, K, ldw, lds;
+    float eps;
+    const float* bias;      // [N_out] or null; not with SWIGLU
+    int rms_plain;          // RMS-normalise x without a weight vector (folded into W before quantisation)
+    int ldx, ldy, ldres;    // element strides between the rows of x / y / res (MB > 1)
+};
+
+// One 16-byte load per lane is 32 weights = exactly one scale block, so a lane's vector has ONE scale.  A wave owns NP PAIRS of weight rows per
+// trip and keeps 16 vectors per lane (16 KiB per wave, gemv_fp8_kernel's footprint) in flight: rows of K <= 4096 are two vectors per lane, so
+// NP = 4 (eight rows), longer rows NP = 1.  A pair = (gate j, up j) -> one output with SWIGLU, rows (2 jp, 2 jp + 1) without (N even).
+// x lives in LDS in the 16-bit element type as [MB][K], staged exactly as gemv_fp8_kernel stages it.  Per vector the 2 NP rows' dwords are
+// converted once (v_cvt_scalef32_pk_*_fp4, the block scale in the conversion) and every x read from LDS serves all of them; each row's fp32 sum
+// takes its products in k order whatever NP and MB are, so a row of the multi-row form is the single-row form bit for bit.
+// grid = ceil(n_pairs / (4 NP)), block 256; dynamic LDS = MB * K * 2 bytes.  K % 32 == 0, MB * K <= 32704.
+template <bool SWIGLU, bool OUT_F32, int NP, int MB>
+__device__ __forceinline__ void gemv_mxfp4_body(const Gemv4Args& p) {
+#pragma clang fp reassociate(off)                  // the RMSNorm arithmetic in gemv_bf16_kernel's order: the staged x is the same bits
+    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
+    __shared__ float red[MB][4];
+    bf16_t* xs = (bf16_t*)vl2_smem;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_pairs = p.N / 2;
+    const int nvec = p.K >> 5;                       // 16-B vectors (32 weights, one scale block) per row
+    constexpr int SL = 8 / NP;                       // load slots per pair and pass
+    const bool one_pass = nvec <= 64 * SL;
+    u32x4 wv[8], uv[8];
+    uint32_t ws[8], us[8];
+    const int jp0 = (blockIdx.x * 4 + wave) * NP;    // this wave's first pair
+    auto rows_of = [&](int jp, int& r0, int& r1) {
+        r0 = SWIGLU ? (jp >> 5) * 64 + (jp & 31) : 2 * jp;
+        r1 = SWIGLU ? r0 + 32 : r0 + 1;
+    };
+    auto issue_rows = [&](int v0) {
+#pragma unroll
+        for (int pr = 0; pr < NP; ++pr) {
+            int r0, r1;
+            rows_of(jp0 + pr, r0, r1);
+            const bool live = jp0 + pr < n_pairs;
+#pragma unroll
+            for (int i = 0; i < SL; ++i) {
+                const int v = v0 + i * 64 + lane;
+                if (live && v < nvec) {
+                    wv[pr * SL + i] = __builtin_nontemporal_load((const u32x4*)(p.W + (size_t)r0 * p.ldw + (size_t)v * 16));
+                    uv[pr * SL + i] = __builtin_nontemporal_load((const u32x4*)(p.W + (size_t)r1 * p.ldw + (size_t)v * 16));
+                    ws[pr * SL + i] = p.scale[(size_t)r0 * p.lds + v];
+                    us[pr * SL + i] = p.scale[(size_t)r1 * p.lds + v];
+                }
+            }
+        }
+    };
+    if (one_pass && jp0 < n_pairs) issue_rows(0);    // the weights do not depend on x: their latency overlaps the staging of x
+    float rstd[MB];
+#pragma unroll
+    for (int b = 0; b < MB; ++b) rstd[b] = 1.f;
+    const bool norm = p.norm_w != nullptr || p.rms_plain;
+    if (norm) {
+#pragma unroll
+        for (int b = 0; b < MB; ++b) {
+            float ss = 0.f;
+            for (int k = tid * 8; k < p.K; k += 2048) {
+                float v[8];
+                unpack8(*(const u32x4*)(p.x + (size_t)b * p.ldx + k), v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) red[b][wave] = ss;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < MB; ++b) rstd[b] = rsqrtf(((red[b][0] + red[b][1]) + (red[b][2] + red[b][3])) / (float)p.K + p.eps);
+    }
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+        for (int k = tid * 8; k < p.K; k += 2048) {
+            u32x4 raw = *(const u32x4*)(p.x + (size_t)b * p.ldx + k);
+            if (norm) {
+                float v[8];
+                unpack8(raw, v);
+                f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
+                if (p.norm_w) { w0 = *(const f32x4*)(p.norm_w + k); w1 = *(const f32x4*)(p.norm_w + k + 4); }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd[b]) * (j < 4 ? w0[j] : w1[j - 4]);
+                raw = pack8(v);                      // HF: the norm's output is a 16-bit tensor
+            }
+            *(u32x4*)(xs + (size_t)b * p.K + k) = raw;
+        }
+    __syncthreads();
+    if (jp0 >= n_pairs) return;
+    float a0[NP][MB], a1[NP][MB];
+#pragma unroll
+    for (int pr = 0; pr < NP; ++pr)
+#pragma unroll
+        for (int b = 0; b < MB; ++b) a0[pr][b] = a1[pr][b] = 0.f;
+    for (int v0 = 0; v0 < nvec; v0 += 64 * SL) {
+        if (!one_pass) issue_rows(v0);
+#pragma unroll
+        for (int i = 0; i < SL; ++i) {
+            const int v = v0 + i * 64 + lane;
+            if (v < nvec) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {        // dword q of the vector = k 8q .. 8q+7 of the block
+                    u32x4 e0[NP], e1[NP];
+#pragma unroll
+                    for (int pr = 0; pr < NP; ++pr) {
+                        e0[pr] = mx4_cvt8(wv[pr * SL + i][q], mx4_scale(ws[pr * SL + i]));
+                        e1[pr] = mx4_cvt8(uv[pr * SL + i][q], mx4_scale(us[pr * SL + i]));
+                    }
+#pragma unroll
+                    for (int b = 0; b < MB; ++b) {
+                        const u32x4 xq = *(const u32x4*)(xs + (size_t)b * p.K + (size_t)v * 32 + 8 * q);
+#pragma unroll
+                        for (int pr = 0; pr < NP; ++pr) {
+                            if (jp0 + pr >= n_pairs) continue;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                a0[pr][b] = dot2_bf16(e0[pr][j], xq[j], a0[pr][b]);
+                                a1[pr][b] = dot2_bf16(e1[pr][j], xq[j], a1[pr][b]);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int pr = 0; pr < NP; ++pr) {
+        const int jp = jp0 + pr;
+        if (jp >= n_pairs) continue;
+        int r0, r1;
+        rows_of(jp, r0, r1);
+        float s0[MB], s1[MB];
+#pragma unroll
+        for (int b = 0; b < MB; ++b) { s0[b] = wave_sum(a0[pr][b]); s1[b] = wave_sum(a1[pr][b]); }
+        if (lane == 0) {
+#pragma unroll
+            for (int b = 0; b < MB; ++b) {
+                float t0 = s0[b], t1 = s1[b];
+                const bf16_t* res = p.res ? p.res + (size_t)b * p.ldres : nullptr;
+                if (SWIGLU) {
+                    float o = silu_f(t0) * t1;
+                    if (res) o += bf2f(res[jp]);
+                    ((bf16_t*)p.y)[(size_t)b * p.ldy + jp] = f2bf(o);
+                } else {
+                    if (p.bias) { t0 += p.bias[r0]; t1 += p.bias[r1]; }
+                    if (res) { t0 += bf2f(res[r0]); t1 += bf2f(res[r1]); }
+                    if (OUT_F32) { ((float*)p.y)[(size_t)b * p.ldy + r0] = t0; ((float*)p.y)[(size_t)b * p.ldy + r1] = t1; }
+                    else { ((bf16_t*)p.y)[(size_t)b * p.ldy + r0] = f2bf(t0); ((bf16_t*)p.y)[(size_t)b * p.ldy + r1] = f2bf(t1); }
+                }
+            }
+        }
+    }
+}
+
+template <bool SWIGLU, bool OUT_F32, int NP>
+__global__ __launch_bounds__(256) void gemv_mxfp4_kernel(Gemv4Args p) { gemv_mxfp4_body<SWIGLU, OUT_F32, NP, 1>(p); }
+
+template <bool SWIGLU, bool OUT_F32, int NP, int MB>
+__global__ __launch_bounds__(256) void gemv_mr_mxfp4_kernel(Gemv4Args p) { gemv_mxfp4_body<SWIGLU, OUT_F32, NP, MB>(p); }
+
+// ---- skinny-M GEMM on the MXFP4 weights (W4A16), 5..64 tokens per step:  C[M <= 64, N] = epilogue( A[M,K] . W~[N,K]^T ).
+// gemm_skinny_kernel's grid, K split, x staging and MFMA sequence WITH ITS LANE-TO-K ASSIGNMENT KEPT: per 32-deep step a lane loads the 4 bytes
+// that hold the 8 k of B[k = (lane>>4)*8 + j][n = lane&15] (they lie inside one scale block: one scale byte per load), converts them with the
+// block scale to the element type and feeds v_mfma_f32_16x16x32.  The B operand is therefore the dequantised weight exactly, and the output is
+// bit for bit gemm_skinny_kernel on dequant(q, s) provided the K split is the same -- the launcher picks it from N and K only.  The partials
+// go through the workspace and skinny_reduce_kernel (unscaled form) in order.
+struct Skinny4Args {
+    const bf16_t* A;        // [M, lda]
+    const uint8_t* Q;       // [N, ldq] bytes, two codes each
+    const uint8_t* S;       // [N, lds] E8M0 bytes
+    float* part;            // [KS][Mp][N] fp32 partial sums, Mp = 16 * MT
+    int M, N, K, lda, ldq, lds;
+    int kslice, kchunk;     // K per workgroup (multiple of kchunk), K per LDS chunk (multiple of 32)
+};
+
+// grid = (N/64, KS), block 256; dynamic LDS = Mp * (kchunk + 8) * 2 bytes
+template <int MT>
+__global__ __launch_bounds__(256) void gemm_skinny_mxfp4_kernel(Skinny4Args p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
+    constexpr int Mp = 16 * MT;
+    constexpr int NL = 16;                                // weight loads in flight per lane
+    bf16_t* xs = (bf16_t*)vl2_smem;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n0 = blockIdx.x * 64 + wave * 16;
+    const int k0 = blockIdx.y * p.kslice;
+    const int pitch = p.kchunk + 8;
+    const int l15 = lane & 15, lg = lane >> 4;
+    const uint8_t* wrow = p.Q + (size_t)(n0 + l15) * p.ldq + (k0 >> 1) + lg * 4;
+    const uint8_t* srow = p.S + (size_t)(n0 + l15) * p.lds + (k0 >> 5);
+
+    f32x4v acc[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = f32x4v{0.f, 0.f, 0.f, 0.f};
+
+    const int cvec = p.kchunk >> 3;
+    for (int kc = 0; kc < p.kslice; kc += p.kchunk) {
+        const int nstep = p.kchunk >> 5;
+        uint32_t wv[NL], sv[NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i)
+            if (i < nstep) {
+                wv[i] = __builtin_nontemporal_load((const uint32_t*)(wrow + (kc >> 1) + i * 16));
+                sv[i] = srow[(kc >> 5) + i];
+            }
+        __syncthreads();
+        for (int e = tid; e < Mp * cvec; e += 256) {
+            const int r = e / cvec, c = e - r * cvec;
+            u32x4 v = u32x4{0u, 0u, 0u, 0u};
+            if (r < p.M) v = *(const u32x4*)(p.A + (size_t)r * p.lda + k0 + kc + c * 8);
+            *(u32x4*)(xs + (size_t)r * pitch + c * 8) = v;
+        }
+        __syncthreads();
+        for (int s0 = 0; s0 < nstep; s0 += NL) {
+            if (s0) {
+#pragma unroll
+                for (int i = 0; i < NL; ++i)
+                    if (s0 + i < nstep) {
+                        wv[i] = __builtin_nontemporal_load((const uint32_t*)(wrow + (kc >> 1) + (s0 + i) * 16));
+                        sv[i] = srow[(kc >> 5) + s0 + i];
+                    }
+            }
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                if (s0 + i < nstep) {
+                    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, mx4_cvt8(wv[i], mx4_scale(sv[i])));
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) {
+                        const bf16x8 afrag = *(const bf16x8*)(xs + (size_t)(m * 16 + l15) * pitch + (s0 + i) * 32 + lg * 8);
+                        acc[m] = VL2_MFMA16(afrag, bfrag, acc[m]);
+                    }
+                }
+            }
+        }
+    }
+    float* dst = p.part + (size_t)blockIdx.y * Mp * p.N;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[(size_t)(m * 16 + lg * 4 + r) * p.N + n0 + l15] = acc[m][r];
+}

@@ -31,6 +31,7 @@ static constexpr bool kLab = false;
 #include "k_sample.h"
 #include "k_skinny.h"
 #include "k_skinny_fp8.h"
+#include "k_mxfp4.h"
 #include "k_stc.h"
 #include "k_vit.h"
 #include "k_moe.h"
@@ -1395,6 +1396,120 @@ extern "C" int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const
         b0 += mb;
     }
     return launched("vl2_gemv_batched_fp8");
+}
+// ---- MXFP4 weights (k_mxfp4.h): q [N, ldq] bytes of two E2M1 codes, s [N, lds] E8M0 bytes (one per 32 k).  Every check precedes every launch.
+extern "C" int32_t vl2_pack_quant_mxfp4(const void* w, int64_t N, int64_t K, int64_t ldw, void* q, void* s, int64_t lds, void* stream) {
+    if (!w) return fail(VL2_E_BADARG, "vl2_pack_quant_mxfp4: null w (the 16-bit weights)");
+    if (!q) return fail(VL2_E_BADARG, "vl2_pack_quant_mxfp4: null q (the E2M1 codes)");
+    if (!s) return fail(VL2_E_BADARG, "vl2_pack_quant_mxfp4: null scale (the E8M0 block scales)");
+    if (N <= 0 || K <= 0 || N > 0x7fffffff || K > 0x7fffffff) return fail(VL2_E_BADARG, "vl2_pack_quant_mxfp4: empty or oversized shape");
+    if (K % 32) return fail(VL2_E_SHAPE, "vl2_pack_quant_mxfp4: need K%%32==0 (one scale per block of 32; K=%lld)", (long long)K);
+    if (ldw % 8 || ldw < K || lds < K / 32 || !ALIGNED16(w) || !ALIGNED16(q))
+        return fail(VL2_E_SHAPE, "vl2_pack_quant_mxfp4: need 16-byte aligned rows, ldw%%8==0, ldw>=K, lds>=K/32");
+    hipLaunchKernelGGL(quant_mxfp4_rows_kernel, dim3((unsigned)N), dim3(256), 0, ST(stream), (const bf16_t*)w, (uint8_t*)q, (uint8_t*)s, (int)K, (long)ldw,
+                       (long)(K / 2), (long)lds);
+    return launched("vl2_pack_quant_mxfp4");
+}
+// rows of K <= 4096 are two 16-B vectors per lane: four pairs per wave and trip keep 16 KiB per wave in flight (k_mxfp4.h); MB = 1 is
+// gemv_mxfp4_kernel, MB = 2..4 gemv_mr_mxfp4_kernel -- one body
+template <bool SW, bool F32>
+static void launch_gemv_mxfp4_rows(const Gemv4Args& a, int mb, hipStream_t s) {
+    const size_t lds = (size_t)mb * a.K * 2;
+    const dim3 b(256);
+#define VL2_G4(NP)                                                                                            \
+    do {                                                                                                      \
+        const dim3 g((unsigned)((a.N / 2 + 4 * NP - 1) / (4 * NP)));                                          \
+        if (mb == 1) hipLaunchKernelGGL((gemv_mxfp4_kernel<SW, F32, NP>), g, b, lds, s, a);                   \
+        else if (mb == 2) hipLaunchKernelGGL((gemv_mr_mxfp4_kernel<SW, F32, NP, 2>), g, b, lds, s, a);        \
+        else if (mb == 3) hipLaunchKernelGGL((gemv_mr_mxfp4_kernel<SW, F32, NP, 3>), g, b, lds, s, a);        \
+        else hipLaunchKernelGGL((gemv_mr_mxfp4_kernel<SW, F32, NP, 4>), g, b, lds, s, a);                     \
+    } while (0)
+    if (a.K <= 4096) VL2_G4(4); else VL2_G4(1);
+#undef VL2_G4
+}
+static int32_t gemv_mxfp4_rows(const char* who, const void* q, const void* sc, int32_t lds, const void* x, const float* norm_w, const void* res,
+                               const float* bias, void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres,
+                               float eps, int32_t flags, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "%s: null q (the E2M1 codes)", who);
+    if (!sc) return fail(VL2_E_BADARG, "%s: null scale (the E8M0 block scales)", who);
+    if (!x || !y || N <= 0 || K <= 0 || MB <= 0) return fail(VL2_E_BADARG, "%s: null pointer or empty shape", who);
+    if (K % 32) return fail(VL2_E_SHAPE, "%s: need K%%32==0 (one scale per block of 32; K=%d)", who, K);
+    if (K > 32704) return fail(VL2_E_SHAPE, "%s: need K<=32704 (x lives in LDS as 16-bit elements; K=%d)", who, K);
+    if (N % 2) return fail(VL2_E_SHAPE, "%s: need N even (N=%d)", who, N);
+    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
+    const int n_out = sw ? N / 2 : N;
+    if (ldq % 16 || ldq < K / 2 || lds < K / 32 || ldx % 8 || ldx < K || ldy < n_out || (res && (ldres < n_out)) || !ALIGNED16(q) || !ALIGNED16(x))
+        return fail(VL2_E_SHAPE, "%s: need 16-byte aligned rows, ldq%%16==0, ldq>=K/2, lds>=K/32, ldx%%8==0, ldx>=K, ldy / ldres >= the output width", who);
+    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "%s: SWIGLU excludes bias / f32 output", who);
+    if (sw && N % 64) return fail(VL2_E_SHAPE, "%s: SWIGLU needs N%%64==0 (N=%d)", who, N);
+    const int esz = f32 ? 4 : 2;
+    const int fit = (65536 - 64) / (K * 2), cap = fit < 4 ? fit : 4;  // x rows that fit the 64 KiB of LDS (beside the norm's 64 B), at most 4 per pass
+    const bool plain = flags & VL2_GEMV_RMS_PLAIN;
+    for (int b0 = 0; b0 < MB;) {
+        const int mb = MB - b0 < cap ? MB - b0 : cap;
+        Gemv4Args a{(const uint8_t*)q, (const uint8_t*)sc, (const bf16_t*)x + (size_t)b0 * ldx, plain ? nullptr : norm_w,
+                    res ? (const bf16_t*)res + (size_t)b0 * ldres : nullptr, (char*)y + (size_t)b0 * ldy * esz, N, K, ldq, lds, eps, bias, plain ? 1 : 0,
+                    ldx, ldy, ldres};
+        if (sw) launch_gemv_mxfp4_rows<true, false>(a, mb, ST(stream));
+        else if (f32) launch_gemv_mxfp4_rows<false, true>(a, mb, ST(stream));
+        else launch_gemv_mxfp4_rows<false, false>(a, mb, ST(stream));
+        b0 += mb;
+    }
+    return launched(who);
+}
+extern "C" int32_t vl2_gemv_mxfp4(const void* q, const void* scale, int32_t lds, const void* x, const float* norm_w, const void* res, const float* bias,
+                                  void* y, int32_t N, int32_t K, int32_t ldq, float eps, int32_t flags, void* stream) {
+    const int n_out = (flags & VL2_GEMM_SWIGLU) ? N / 2 : N;
+    return gemv_mxfp4_rows("vl2_gemv_mxfp4", q, scale, lds, x, norm_w, res, bias, y, 1, N, K, ldq, K, n_out, n_out, eps, flags, stream);
+}
+extern "C" int32_t vl2_gemv_batched_mxfp4(const void* q, const void* scale, int32_t lds, const void* x, const float* norm_w, const void* res,
+                                          const float* bias, void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy,
+                                          int32_t ldres, float eps, int32_t flags, void* stream) {
+    return gemv_mxfp4_rows("vl2_gemv_batched_mxfp4", q, scale, lds, x, norm_w, res, bias, y, MB, N, K, ldq, ldx, ldy, ldres, eps, flags, stream);
+}
+// skinny-M on the MXFP4 weights: vl2_gemm_skinny_fp8's grid, K split (from N and K only, never shrunk to fit the workspace), chunking and ordered
+// reduce; the block scales ride in the conversion, so the reduce is the unscaled one
+template <int MT>
+static void launch_skinny_mxfp4(const Skinny4Args& a, int ks, size_t lds, hipStream_t s) {
+    lds_attr<gemm_skinny_mxfp4_kernel<MT>>(65536);
+    hipLaunchKernelGGL((gemm_skinny_mxfp4_kernel<MT>), dim3(a.N / 64, ks), dim3(256), lds, s, a);
+}
+extern "C" int32_t vl2_gemm_skinny_mxfp4(const void* A, const void* q, const void* scale, int32_t lds_, void* C, const float* bias, const void* res,
+                                         int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws,
+                                         int64_t ws_bytes, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: null q (the E2M1 codes)");
+    if (!scale) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: null scale (the E8M0 block scales)");
+    if (!A || !C || M <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: null pointer or empty shape");
+    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
+    if (M > 64) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: M=%d rows, need M<=64 (split larger batches)", M);
+    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
+    if (K % 32) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: need K%%32==0 (K=%d)", K);
+    if (lda % 8 || lda < K || ldq % 16 || ldq < K / 2 || lds_ < K / 32 || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(q))
+        return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: need 16-byte aligned rows, lda%%8==0, ldq%%16==0, ldq>=K/2, lds>=K/32, ldc%%4==0, ldres%%4==0");
+    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemm_skinny_mxfp4: SWIGLU excludes bias / f32 output");
+    if (!ws || !ALIGNED16(ws) || ws_bytes <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: needs a 16-byte aligned workspace (fp32 partial sums)");
+    const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4, Mp = 16 * mt;
+    const int steps = K / 32;
+    int ks = (4096 + N / 16 - 1) / (N / 16);
+    ks = ks < 1 ? 1 : ks > 32 ? 32 : ks;
+    while (ks > 1 && steps % ks) --ks;
+    if ((int64_t)ks * Mp * N * 4 > ws_bytes)
+        return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)ks * Mp * N * 4);
+    const int kslice = K / ks;
+    int kchunk = kslice;
+    while (kchunk > 32 && (kslice % kchunk || kchunk % 32 || (size_t)Mp * (kchunk + 8) * 2 > 65536)) kchunk -= 32;
+    if (kslice % kchunk || (size_t)Mp * (kchunk + 8) * 2 > 65536) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: no K chunking for K=%d", K);
+    Skinny4Args a{(const bf16_t*)A, (const uint8_t*)q, (const uint8_t*)scale, (float*)ws, M, N, K, lda, ldq, lds_, kslice, kchunk};
+    const size_t lds = (size_t)Mp * (kchunk + 8) * 2;
+    hipStream_t s = ST(stream);
+    if (mt == 1) launch_skinny_mxfp4<1>(a, ks, lds, s); else if (mt == 2) launch_skinny_mxfp4<2>(a, ks, lds, s); else launch_skinny_mxfp4<4>(a, ks, lds, s);
+    SkinnyReduceArgs r{(const float*)ws, C, bias, (const bf16_t*)res, M, Mp, N, ks, ldc, ldres};
+    const int ncol = sw ? N / 2 : N;
+    const dim3 g((M * (ncol / 4) + 255) / 256), b(256);
+    if (sw) hipLaunchKernelGGL((skinny_reduce_kernel<true, false>), g, b, 0, s, r);
+    else if (f32) hipLaunchKernelGGL((skinny_reduce_kernel<false, true>), g, b, 0, s, r);
+    else hipLaunchKernelGGL((skinny_reduce_kernel<false, false>), g, b, 0, s, r);
+    return launched("vl2_gemm_skinny_mxfp4");
 }
 extern "C" int32_t vl2_attn_decode(const void* qkv, void* kcache, void* vcache, const float* cos_t, const float* sin_t,
                                    float* partial, void* out, int32_t nh, int32_t nkv, int32_t smax, int32_t pos,

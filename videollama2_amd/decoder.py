@@ -20,16 +20,17 @@ def eos_set(eos_token_id):
 
 
 # ---------------------------------------------------------------------- projection forms
-# A form is the kernel family that projects a layer's activations, picked once per call from the path and the fp8 switches.  The two
-# layer loops (HipMistralDecoder._rows / _tokens) ask it for normed(x, w) = RMSNorm(x) @ w.T (the norm weight is folded into w: q/k/v,
-# gate/up), res(a, w, x) = x + a @ w.T (o, down) and, in the token loop, head(x, out) = the fp32 logits.  `layers` holds the per-layer
-# weights it reads (the 16-bit dicts or their fp8 copies).  16-bit forms under tensor parallelism: the residual rides on rank 0's partial
-# sum and the result is all-reduced; the fp8 forms are single-rank and issue no all-reduce.
+# A form is the kernel family that projects a layer's activations, picked once per call from the path and the weight format ("16bit" |
+# "fp8" | "mxfp4").  The two layer loops (HipMistralDecoder._rows / _tokens) ask it for normed(x, w) = RMSNorm(x) @ w.T (the norm weight
+# is folded into w: q/k/v, gate/up), res(a, w, x) = x + a @ w.T (o, down) and, in the token loop, head(x, out) = the fp32 logits.
+# `layers` holds the per-layer weights it reads (the 16-bit dicts, or their fp8 / MXFP4 copies as (codes, scales) pairs); lm_head is
+# quantised in fp8 only, the MXFP4 forms run the 16-bit one.  16-bit forms under tensor parallelism: the residual rides on rank 0's
+# partial sum and the result is all-reduced; the quantised forms are single-rank and issue no all-reduce.
 class _Form:
-    def __init__(self, dec, fp8=False):
-        self.dec, self.fp8 = dec, fp8
-        w = dec.w8 if fp8 else dec.w
-        self.layers, self.lm_head = w["layers"], w["lm_head"]
+    def __init__(self, dec, fmt="16bit"):
+        self.dec, self.fmt = dec, fmt
+        w = dec.w if fmt == "16bit" else dec.w8 if fmt == "fp8" else dec.w4
+        self.layers, self.lm_head = w["layers"], (dec.w8 if fmt == "fp8" else dec.w)["lm_head"]
 
     def begin(self, x):
         """The rows loop's prologue: (0, rstd) of x's rows in rn, which the carried norm reads and Mixtral's MoE combine keeps current."""
@@ -37,7 +38,7 @@ class _Form:
         self.rn = ops.row_norm_finalize(self.rs, self.dec.D, ops.NORM_RMS, self.dec.eps)
 
     def res(self, a, w, x, out=None):
-        if self.fp8:
+        if self.fmt != "16bit":
             return self._mm(a, w, res=x, out=out)
         dec = self.dec
         return dec._reduce(self._mm(a, w, res=x if dec.tp_rank == 0 else None, out=out))
@@ -65,7 +66,7 @@ class _W8A8(_Form):
     """fp8 weights and fp8 activations, quantised per row on the fly (with the row's RMS for a normed projection)."""
 
     def __init__(self, dec):
-        super().__init__(dec, fp8=True)
+        super().__init__(dec, "fp8")
 
     def begin(self, x):
         pass
@@ -79,36 +80,44 @@ class _W8A8(_Form):
 
 class _Skinny(_Form):
     """RMSNorm as its own launch, then the skinny-M MFMA kernel: the weights stream once for up to 64 rows (16-bit: the tiled GEMM
-    beyond; fp8: calls of at most 64 rows)."""
+    beyond; fp8 / MXFP4: calls of at most 64 rows)."""
+    QUANTISED = dict(fp8=ops.gemm_skinny_fp8, mxfp4=ops.gemm_skinny_mxfp4)
 
-    def __init__(self, dec, fp8, rows):
-        super().__init__(dec, fp8)
-        self._mm = (lambda a, w, **kw: ops.gemm_skinny_fp8(a, *w, **kw)) if fp8 else ops.gemm_skinny if rows <= 64 else ops.gemm
+    def __init__(self, dec, fmt, rows):
+        super().__init__(dec, fmt)
+        mm16 = ops.gemm_skinny if rows <= 64 else ops.gemm
+        self._mm = mm16 if fmt == "16bit" else (lambda a, w, kern=self.QUANTISED[fmt], **kw: kern(a, *w, **kw))
+        self._head = mm16 if fmt == "mxfp4" else self._mm
 
     def normed(self, x, w, **kw):
         return self._mm(ops.rmsnorm(x, self.dec.w["ones"], self.dec.eps), w, **kw)
 
     def head(self, x, out):
-        return self._mm(ops.rmsnorm(x, self.dec.w["norm_w"], self.dec.eps), self.lm_head, out_f32=True, out=out)
+        return self._head(ops.rmsnorm(x, self.dec.w["norm_w"], self.dec.eps), self.lm_head, out_f32=True, out=out)
 
 
 class _Gemv(_Form):
-    """GEMV with the RMSNorm fused into the kernel (fp8: plain RMS, the weight folded in), one row or a few (batched: one pass over the
-    weights for all rows, each bit for bit the single-row call)."""
+    """GEMV with the RMSNorm fused into the kernel (fp8 / MXFP4: plain RMS, the weight folded in), one row or a few (batched: one pass
+    over the weights for all rows, each bit for bit the single-row call)."""
+    KERNELS = {"16bit": (ops.gemv, ops.gemv_batched), "fp8": (ops.gemv_fp8, ops.gemv_batched_fp8),
+               "mxfp4": (ops.gemv_mxfp4, ops.gemv_batched_mxfp4)}
 
-    def __init__(self, dec, fp8, batched):
-        super().__init__(dec, fp8)
-        self._mv = (ops.gemv_batched_fp8 if batched else ops.gemv_fp8) if fp8 else (ops.gemv_batched if batched else ops.gemv)
+    def __init__(self, dec, fmt, batched):
+        super().__init__(dec, fmt)
+        self._mv = self.KERNELS[fmt][batched]
+        self._head_fmt = "16bit" if fmt == "mxfp4" else fmt
+        self._head_mv = self.KERNELS[self._head_fmt][batched]
 
     def _mm(self, a, w, **kw):
-        return self._mv(*w, a, **kw) if self.fp8 else self._mv(w, a, **kw)
+        return self._mv(w, a, **kw) if self.fmt == "16bit" else self._mv(*w, a, **kw)
 
     def normed(self, x, w, **kw):
-        fold = dict(rms_plain=True) if self.fp8 else dict(norm_w=self.dec.w["ones"])
+        fold = dict(norm_w=self.dec.w["ones"]) if self.fmt == "16bit" else dict(rms_plain=True)
         return self._mm(x, w, eps=self.dec.eps, **fold, **kw)
 
     def head(self, x, out):
-        return self._mm(x, self.lm_head, norm_w=self.dec.w["norm_w"], eps=self.dec.eps, out_f32=True, out=out)
+        w = (self.lm_head,) if self._head_fmt == "16bit" else self.lm_head
+        return self._head_mv(*w, x, norm_w=self.dec.w["norm_w"], eps=self.dec.eps, out_f32=True, out=out)
 
 
 class HipMistralDecoder(nn.Module):
@@ -166,7 +175,12 @@ class HipMistralDecoder(nn.Module):
         # validation hook for 1-GPU boxes: issue the tensor-parallel all-reduces even when the group has ONE rank (the sum over one
         # rank is the identity), so that the captured-RCCL decode graph can be exercised on hardware without a second GPU
         self.tp_always_reduce = False
-        self.decode_fp8 = self.prefill_fp8 = False
+        self.decode_fp8 = self.prefill_fp8 = self.decode_mxfp4 = False
+
+    @property
+    def decode_format(self):
+        """The weight format of the decode step's projections: "16bit" | "fp8" | "mxfp4"."""
+        return "mxfp4" if self.decode_mxfp4 else "fp8" if self.decode_fp8 else "16bit"
 
     @torch.no_grad()
     def enable_fp8_decode(self, on=True):
@@ -176,10 +190,32 @@ class HipMistralDecoder(nn.Module):
         (+7.2 GB for the 7B model).  Not the reference's arithmetic and never the default: oracle/fp8_oracle.py defines the quantiser."""
         if self.tp > 1:
             raise NotImplementedError("fp8 decode weights: single-rank decoders only")
+        if on and self.decode_mxfp4:
+            raise ValueError("MXFP4 decode weights are on: call enable_mxfp4_decode(False) before enable_fp8_decode()")
         if on and getattr(self, "w8", None) is None:
             self._make_w8()
         self.decode_fp8 = bool(on)
         self._invalidate_graphs()                                 # a captured step (greedy or sampled) holds the other projections
+        self.cache_epoch += 1
+        return self
+
+    @torch.no_grad()
+    def enable_mxfp4_decode(self, on=True):
+        """OPTIONAL arithmetic: the decode step's projections stream MXFP4 copies of the packed weights (OCP Microscaling Formats v1.0: E2M1
+        elements, one E8M0 power-of-two scale per block of 32 k, 4.25 bits per weight; csrc/k_mxfp4.h; activations stay 16-bit).  Copies of
+        wqkv / wo / wgu / wd of every layer are made once, here, from the packed weights (self.w4, +1.8 GB for the 7B model).  lm_head STAYS
+        16-bit: its error lands on the logits directly and it is 0.26 GB of a 4 GB stream.  Prefill, extend, attention, RoPE, the KV cache
+        and the embedding stay 16-bit too (the fp8 prefill may be on beside it).  The single-token step then runs operator by operator (it is
+        replayed from a hipGraph anyway; the stage call knows no MXFP4).  Not the reference's arithmetic and never the default: the format
+        costs about 11 % rel-L2 per projection; tests/mxfp4_oracle.py defines the quantiser."""
+        if self.tp > 1:
+            raise NotImplementedError("MXFP4 decode weights: single-rank decoders only")
+        if on and self.decode_fp8:
+            raise ValueError("fp8 decode weights are on: call enable_fp8_decode(False) before enable_mxfp4_decode()")
+        if on and getattr(self, "w4", None) is None:
+            self.w4 = dict(layers=[{k: ops.quant_mxfp4(lw[k]) for k in ("wqkv", "wo", "wgu", "wd")} for lw in self.w["layers"]])
+        self.decode_mxfp4 = bool(on)
+        self._invalidate_graphs()                                 # a captured step holds the other projections
         self.cache_epoch += 1
         return self
 
@@ -193,7 +229,7 @@ class HipMistralDecoder(nn.Module):
 
     def _invalidate_graphs(self):
         """Drop every captured decode graph: the greedy one and the sampled one (keyed by the sampler only) both bake in the weight
-        pointers / arithmetic (`decode_fp8`) and the stage workspace of the moment they were captured; so do the batched steps' graphs
+        pointers / arithmetic (`decode_format`) and the stage workspace of the moment they were captured; so do the batched steps' graphs
         (capture_batch_graph), which the next step captures again on the weights then selected."""
         self.graph = None
         self._graph_sample = (None, None)
@@ -325,7 +361,7 @@ class HipMistralDecoder(nn.Module):
             raise ValueError(f"sequence length {P + n} exceeds the KV cache ({self.max_seq_len})")
         self.cache_epoch += 1
         x = x_new.to(device=self._dev, dtype=_lib.elem_dtype()).contiguous()
-        f = _Skinny(self, False, n) if n <= self.EXTEND_SKINNY_ROWS else _Tiled(self)
+        f = _Skinny(self, "16bit", n) if n <= self.EXTEND_SKINNY_ROWS else _Tiled(self)
         out = self.logits if logits_out is None else logits_out
         x = self._rows(f, x, [(0, n, P, self.kcache, self.vcache)], (out,), append=n <= self.EXTEND_APPEND_ROWS)
         self.pos = P + n
@@ -352,7 +388,7 @@ class HipMistralDecoder(nn.Module):
     def _decode_kernels(self, dyn):
         """Enqueue one decode step for the token in self.tok: embed -> 32 x {qkv GEMV (+RMSNorm), RoPE+append+attention,
         o GEMV (+res), gate/up GEMV (+RMSNorm, SwiGLU), down GEMV (+res)} -> lm_head GEMV (+final RMSNorm) into self.logits, on the
-        16-bit weights or their fp8 copies (enable_fp8_decode).  dyn=True reads the position from self.state[0] on the device
+        16-bit weights, their fp8 copies (enable_fp8_decode) or their MXFP4 copies (enable_mxfp4_decode; lm_head 16-bit).  dyn=True reads the position from self.state[0] on the device
         (hipGraph-replayable); no allocation either way."""
         b = self._b
         pos_dev = self.state[0:1] if dyn else None
@@ -361,7 +397,7 @@ class HipMistralDecoder(nn.Module):
         def attend(li, qkv, o):
             ops.attn_decode(qkv, self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, self.partial, o, self.nh, self.nkv,
                             self.pos, self.hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
-        self._tokens(_Gemv(self, self.decode_fp8, batched=False), attend, b["x0"][0], b["x1"], b["qkv"], b["o"], b["a"], self.logits)
+        self._tokens(_Gemv(self, self.decode_format, batched=False), attend, b["x0"][0], b["x1"], b["qkv"], b["o"], b["a"], self.logits)
 
     @torch.no_grad()
     def decode_step(self, tok_dev=None):
@@ -393,7 +429,7 @@ class HipMistralDecoder(nn.Module):
             if sampler is not None:                           # (the stage call opens with its own argmax: the sampled step is the operator sequence)
                 ops.sample_token(self.logits, self.tok, self.u_buf, sampler[0], sampler[1], sampler[2], hist=self.hist, state=self.state)
                 self._decode_kernels(dyn=True)
-            elif self._use_stage():
+            elif self._use_stage() and not self.decode_mxfp4:        # (the stage call knows the 16-bit and the fp8 weights)
                 d, _, ws = self._stage_desc()
                 ops.llm_decode_step(d, self.logits, self.tok, self.state, self.hist, self.partial, ws, fp8=self.decode_fp8)
             else:
@@ -564,7 +600,8 @@ class HipMistralDecoder(nn.Module):
         rounding, not to the bit.
         With enable_fp8_decode the same step streams the fp8 copies (W8A16): the multi-row fp8 GEMV below GEMM_BATCH (a row is bit-identical
         to the single-sequence fp8 step), the fp8 skinny-M kernel from GEMM_BATCH on, in calls of at most 64 rows (bit-identical to the 16-bit
-        skinny-M step on the dequantised weights)."""
+        skinny-M step on the dequantised weights).  With enable_mxfp4_decode: the same two paths on the MXFP4 copies, with the same guarantees
+        against the solo MXFP4 step and the dequantised weights; lm_head on the 16-bit kernels."""
         bb = self._bb
         x = bb["x0"][:nb]
         ops.embed_rows(bb["tok"][:nb], self.w["embed"], x)
@@ -572,9 +609,9 @@ class HipMistralDecoder(nn.Module):
             # M = nb rows: every projection is a few-tile grid, bound by how many workgroups stream the weights.  Split-K (partials
             # through the workspace) measured no gain here (B=16 8.09 vs 8.01 ms per step): the fp32 partial exchange costs what it saves
             ops.set_splitk(False)
-            f = _Skinny(self, self.decode_fp8, nb)
+            f = _Skinny(self, self.decode_format, nb)
         else:
-            f = _Gemv(self, self.decode_fp8, batched=True)
+            f = _Gemv(self, self.decode_format, batched=True)
 
         def attend(li, qkv, o):
             ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, self.nh, self.nkv,
@@ -602,7 +639,7 @@ class HipMistralDecoder(nn.Module):
         """{the draws + the whole batched decode step} as ONE hipGraph per (batch size, sampled) (tokens, positions and the
         draw settings live on the device, so the same graph replays for every step).  sampled=False: one argmax launch per
         request; sampled=True: one ops.sample_tokens launch for all nb rows, whatever mix of greedy and sampled slots they hold.
-        enable_fp8_decode(on / off) drops them all (_invalidate_graphs): the next step captures the weights then selected."""
+        enable_fp8_decode / enable_mxfp4_decode (on / off) drop them all (_invalidate_graphs): the next step captures the weights then selected."""
         graphs = self.__dict__.setdefault("_batch_graphs", {})
         key = (nb, bool(sampled))
         if key in graphs:
@@ -720,6 +757,9 @@ class HipMixtralDecoder(HipMistralDecoder):
 
     def enable_fp8_prefill(self, on=True):
         raise NotImplementedError("MoE (mixtral) decoder: fp8 weights not built")
+
+    def enable_mxfp4_decode(self, on=True):
+        raise NotImplementedError("MoE (mixtral) decoder: MXFP4 weights not built")
 
     def prefill_batch(self, xs, caches, logits_out):
         raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")

@@ -454,6 +454,71 @@ def gemv_batched_fp8(q, scale, x, norm_w=None, eps=1e-5, res=None, swiglu=False,
     return out
 
 
+def quant_mxfp4(w):
+    """include/vl2hip.h vl2_pack_quant_mxfp4: 16-bit weights [N, K], K % 32 == 0 -> (q uint8 [N, K / 2]: two E2M1 codes per byte, k = 2j in bits
+    3:0; s uint8 [N, K / 32]: one E8M0 scale per block of 32)."""
+    _chk(w, _lib.elem_dtype(), "w")
+    N, K = w.shape
+    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    s = torch.empty((N, K // 32), dtype=torch.uint8, device=w.device)
+    _lib.call("vl2_pack_quant_mxfp4", _p(w), N, K, w.stride(0), _p(q), _p(s), s.stride(0), _stream())
+    return q, s
+
+
+def _mxfp4_args(q, s, x, bias, res):
+    _chk(q, torch.uint8, "q"); _chk(s, torch.uint8, "s"); _chk(x, _lib.elem_dtype(), "x"); _chk(bias, torch.float32, "bias")
+    _chk(res, _lib.elem_dtype(), "res")
+    N, K = q.shape[0], q.shape[1] * 2
+    if s.shape[0] != N or s.shape[1] * 32 != K or x.shape[-1] != K:
+        raise ValueError(f"mxfp4: q {tuple(q.shape)}, s {tuple(s.shape)} and x {tuple(x.shape)} do not agree")
+    return N, K
+
+
+def gemv_mxfp4(q, s, x, norm_w=None, eps=1e-5, res=None, swiglu=False, out_f32=False, out=None, bias=None, rms_plain=False):
+    """y = W~ x (+ bias) (+ res) for one token on MXFP4 weights (include/vl2hip.h vl2_gemv_mxfp4; W4A16): q, s from `quant_mxfp4`."""
+    N, K = _mxfp4_args(q, s, x, bias, res)
+    n_out = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((n_out,), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
+    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    _lib.call("vl2_gemv_mxfp4", _p(q), _p(s), s.stride(0), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), N, K, q.stride(0), float(eps), flags,
+              _stream())
+    return out
+
+
+def gemv_batched_mxfp4(q, s, x, norm_w=None, eps=1e-5, res=None, swiglu=False, out_f32=False, out=None, bias=None, rms_plain=False):
+    """y[b] = gemv_mxfp4(q, s, x[b], ...) for the rows of x [MB, K] in one pass over q per launch of up to 4 rows (include/vl2hip.h
+    vl2_gemv_batched_mxfp4): every row bit for bit the single-row call.  res / out are [MB, n_out]."""
+    N, K = _mxfp4_args(q, s, x, bias, res)
+    MB = x.shape[0]
+    n_out = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((MB, n_out), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
+    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    _lib.call("vl2_gemv_batched_mxfp4", _p(q), _p(s), s.stride(0), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), MB, N, K, q.stride(0),
+              x.stride(0), out.stride(0), 0 if res is None else res.stride(0), float(eps), flags, _stream())
+    return out
+
+
+def gemm_skinny_mxfp4(a, q, s, bias=None, res=None, swiglu=False, out_f32=False, out=None):
+    """C = epilogue(a @ W~.T) on MXFP4 weights (include/vl2hip.h vl2_gemm_skinny_mxfp4; W4A16).  Bit for bit `gemm_skinny(a, dequant(q, s))`.
+    More than 64 rows run as calls of at most 64 rows each (the weights stream once per call; a row's bits do not depend on the chunk it
+    lands in).  Needs `attach_workspace`."""
+    N, K = _mxfp4_args(q, s, a, bias, res)
+    M = a.shape[0]
+    ncol = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((M, ncol), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=a.device)
+    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0)
+    ws = attach_workspace(a.device)
+    for m0 in range(0, M, 64):
+        m1 = min(M, m0 + 64)
+        _lib.call("vl2_gemm_skinny_mxfp4", _p(a[m0:m1]), _p(q), _p(s), s.stride(0), _p(out[m0:m1]), _p(bias),
+                  _p(None if res is None else res[m0:m1]), m1 - m0, N, K, a.stride(0), q.stride(0), out.stride(0),
+                  0 if res is None else res.stride(0), flags, _p(ws), ws.numel(), _stream())
+    return out
+
+
 def attn_decode(qkv, kcache, vcache, cos_t, sin_t, partial, out, nh, nkv, pos, scale, pos_dev=None, ctx_cap=0):
     """RoPE + KV append + flash-decoding attention of one new token (un-roped fused qkv row) at position `pos`
     (or *pos_dev, for hipGraph replay; then ctx_cap bounds the positions the launch covers)."""

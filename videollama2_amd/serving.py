@@ -33,8 +33,8 @@ class ContinuousBatcher:
     """decoder: HipMistralDecoder.  max_slots: requests decoding together (<= 4 keeps every request bit-identical to its
     solo greedy decode; more switches the step to the skinny-M MFMA path, equal to bf16 rounding).
     use_graph (default: on a GPU): one captured hipGraph per occupancy (highest occupied slot + 1).
-    fp8 decode weights (decoder.enable_fp8_decode()): the steps stream the fp8 copies, with the same guarantees against the solo fp8 decode.
-    Toggling them with requests in flight is allowed: the toggle drops the captured step graphs, the next step runs (and captures) every
+    fp8 / MXFP4 decode weights (decoder.enable_fp8_decode() / enable_mxfp4_decode()): the steps stream those copies, with the same guarantees
+    against the solo decode on the same copies.  Toggling them with requests in flight is allowed: the toggle drops the captured step graphs, the next step runs (and captures) every
     slot on the weights then selected, and the decoder's cache_epoch is bumped as for any toggle."""
 
     def __init__(self, decoder, max_slots=4, eos_token_id=None, use_graph=None):
