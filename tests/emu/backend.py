@@ -20,7 +20,7 @@ def emulated_backend():
     lib.vl2_stc_workspace_bytes.argtypes = [ctypes.POINTER(_lib.StcDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     lib.vl2_llm_workspace_bytes.restype = ctypes.c_int64
     lib.vl2_llm_workspace_bytes.argtypes = [ctypes.POINTER(_lib.LlmDesc), ctypes.c_int32]
-    for name, args in _lib.SIGNATURES.items():
+    for name, args in {**_lib.SIGNATURES, **_lib.FP8_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int32
         fn.argtypes = args

@@ -18,6 +18,8 @@ alignas(64) unsigned char vl2_smem[160 * 1024];
 #include "k_decode_tail.h"
 #include "k_fp8.h"
 #include "k_skinny.h"
+#include "k_skinny_fp8.h"
+#include "skinny_plan.h"
 #include "k_pack.h"
 #include "k_sample.h"
 #include <cstdint>
@@ -545,41 +547,84 @@ extern "C" int32_t vl2_quant_act_fp8(const void* x, int64_t ldx, void* q, int64_
     emu::launch(dim3((unsigned)M), dim3(256), [=] { quant_act_fp8_kernel((const bf16_t*)x, (long)ldx, (uint8_t*)q, (long)ldq, row_tab, K, norm == 1 ? 1 : 0, eps); });
     return 0;
 }
+// vl2_abi.hip gemv_fp8_rows: one body (k_fp8.h gemv_fp8_body), MB = 1 the single-row kernel; `cap` rows of x per pass
+static int32_t emu_gemv_fp8_rows(int cap, const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
+                                 int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps, int32_t flags) {
+    if (K % 16 || ldq % 16 || ldq < K || N % 2 || MB <= 0) return -2;
+    const bool sw = flags & 1, f32 = flags & 2, plain = flags & VL2_GEMV_RMS_PLAIN;
+    const int esz = f32 ? 4 : 2;
+    dim3 blk(256);
+    for (int b0 = 0; b0 < MB;) {
+        const int mb = MB - b0 < cap ? MB - b0 : cap;
+        Gemv8Args a{(const uint8_t*)q, scale, (const bf16_t*)x + (size_t)b0 * ldx, plain ? nullptr : norm_w, res ? (const bf16_t*)res + (size_t)b0 * ldres : nullptr,
+                    (char*)y + (size_t)b0 * ldy * esz, N, K, ldq, eps, bias, plain ? 1 : 0, ldx, ldy, ldres};
+#define EMU_G8M(SW, F32, NP)                                                                                   \
+        do {                                                                                                   \
+            const dim3 g((N / 2 + 4 * NP - 1) / (4 * NP));                                                     \
+            if (mb == 1) emu::launch(g, blk, [=] { gemv_fp8_kernel<SW, F32, NP>(a); });                        \
+            else if (mb == 2) emu::launch(g, blk, [=] { gemv_mr_fp8_kernel<SW, F32, NP, 2>(a); });             \
+            else if (mb == 3) emu::launch(g, blk, [=] { gemv_mr_fp8_kernel<SW, F32, NP, 3>(a); });             \
+            else emu::launch(g, blk, [=] { gemv_mr_fp8_kernel<SW, F32, NP, 4>(a); });                          \
+        } while (0)
+#define EMU_G8(NP) do { if (sw) EMU_G8M(true, false, NP); else if (f32) EMU_G8M(false, true, NP); else EMU_G8M(false, false, NP); } while (0)
+        if (K <= 4096) EMU_G8(2); else EMU_G8(1);
+#undef EMU_G8
+#undef EMU_G8M
+        b0 += mb;
+    }
+    return 0;
+}
 extern "C" int32_t vl2_gemv_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
                                 int32_t N, int32_t K, int32_t ldq, float eps, int32_t flags, void*) {
-    if (K % 16 || ldq % 16 || ldq < K || N % 2) return -2;
-    Gemv8Args a{(const uint8_t*)q, scale, (const bf16_t*)x, norm_w, (const bf16_t*)res, y, N, K, ldq, eps, bias, 0};
-    if (flags & VL2_GEMV_RMS_PLAIN) { a.norm_w = nullptr; a.rms_plain = 1; }
+    const int n_out = (flags & 1) ? N / 2 : N;
+    return emu_gemv_fp8_rows(1, q, scale, x, norm_w, res, bias, y, 1, N, K, ldq, K, n_out, n_out, eps, flags);
+}
+extern "C" int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias,
+                                        void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps,
+                                        int32_t flags, void*) {
+    return emu_gemv_fp8_rows(4, q, scale, x, norm_w, res, bias, y, MB, N, K, ldq, ldx, ldy, ldres, eps, flags);
+}
+// vl2_abi.hip skinny_rows on the product's plan (skinny_plan.h; the K split from N and K only).  The emulator's shapes are small, so the LDS
+// budget handed to the plan is two chunks' worth: the chunk loop runs more than once where the slice allows it.
+template <class Args, class F1, class F2, class F4>
+static int32_t emu_skinny_rows(Args a, F1 k1, F2 k2, F4 k4, const float* row_scale, void* C, const float* bias, const void* res, int32_t ldc,
+                               int32_t ldres, int32_t flags) {
+    const int M = a.M, N = a.N, K = a.K;
     const bool sw = flags & 1, f32 = flags & 2;
-    dim3 blk(256);
-#define EMU_G8(SW, F32, NP) emu::launch(dim3((N / 2 + 4 * NP - 1) / (4 * NP)), blk, [=] { gemv_fp8_kernel<SW, F32, NP>(a); })
-    if (K <= 4096) { if (sw) EMU_G8(true, false, 2); else if (f32) EMU_G8(false, true, 2); else EMU_G8(false, false, 2); }
-    else           { if (sw) EMU_G8(true, false, 1); else if (f32) EMU_G8(false, true, 1); else EMU_G8(false, false, 1); }
-#undef EMU_G8
+    if (M <= 0 || M > 64 || N % 64 || (sw && N % 128) || K % 32) return -2;
+    SkinnyPlan pl;
+    if (skinny_plan(M, N, K, INT64_MAX, false, pl)) return -2;
+    if (pl.kslice % 64 == 0) skinny_plan(M, N, K, INT64_MAX, false, pl, (size_t)pl.Mp * (pl.kslice / 2 + 8) * 2);
+    static std::vector<float> part;
+    part.assign((size_t)pl.ks * pl.Mp * N, 0.f);
+    a.part = part.data();
+    a.kslice = pl.kslice;
+    a.kchunk = pl.kchunk;
+    const dim3 gk(N / 64, pl.ks), blk(256);
+    if (pl.mt == 1) emu::launch(gk, blk, [=] { k1(a); });
+    else if (pl.mt == 2) emu::launch(gk, blk, [=] { k2(a); });
+    else emu::launch(gk, blk, [=] { k4(a); });
+    SkinnyReduceArgs r{part.data(), C, bias, (const bf16_t*)res, M, pl.Mp, N, pl.ks, ldc, ldres, row_scale};
+    const int ncol = sw ? N / 2 : N;
+    dim3 g((M * (ncol / 4) + 255) / 256);
+#define EMU_SKR(SW, F32) do { if (row_scale) emu::launch(g, blk, [=] { skinny_reduce_kernel<SW, F32, true>(r); }); \
+                              else emu::launch(g, blk, [=] { skinny_reduce_kernel<SW, F32, false>(r); }); } while (0)
+    if (sw) EMU_SKR(true, false); else if (f32) EMU_SKR(false, true); else EMU_SKR(false, false);
+#undef EMU_SKR
     return 0;
 }
 extern "C" int32_t vl2_gemm_skinny_bf16(const void* A, const void* W, void* C, const float* bias, const void* res, int32_t M, int32_t N,
                                         int32_t K, int32_t lda, int32_t ldw, int32_t ldc, int32_t ldres, int32_t flags, void* ws, int64_t ws_bytes, void*) {
     if (!ws || ws_bytes <= 0) return -1;
-    const bool sw = flags & 1, f32 = flags & 2;
-    if (M > 64 || N % 64 || K % 32) return -2;
-    const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4, Mp = 16 * mt, steps = K / 32;
-    int ks = steps % 3 == 0 ? 3 : steps % 2 == 0 ? 2 : 1;       // a small odd / even split exercises the slice + chunk loops
-    const int kslice = K / ks;
-    int kchunk = kslice % 64 == 0 && kslice > 64 ? kslice / 2 : kslice;   // two chunks per slice where possible
-    static std::vector<float> part;
-    part.assign((size_t)ks * Mp * N, 0.f);
-    SkinnyArgs a{(const bf16_t*)A, (const bf16_t*)W, part.data(), M, N, K, lda, ldw, kslice, kchunk};
-    if (mt == 1) emu::launch(dim3(N / 64, ks), dim3(256), [=] { gemm_skinny_kernel<1>(a); });
-    else if (mt == 2) emu::launch(dim3(N / 64, ks), dim3(256), [=] { gemm_skinny_kernel<2>(a); });
-    else emu::launch(dim3(N / 64, ks), dim3(256), [=] { gemm_skinny_kernel<4>(a); });
-    SkinnyReduceArgs r{part.data(), C, bias, (const bf16_t*)res, M, Mp, N, ks, ldc, ldres};
-    const int ncol = sw ? N / 2 : N;
-    dim3 g((M * (ncol / 4) + 255) / 256), blk(256);
-    if (sw) emu::launch(g, blk, [=] { skinny_reduce_kernel<true, false>(r); });
-    else if (f32) emu::launch(g, blk, [=] { skinny_reduce_kernel<false, true>(r); });
-    else emu::launch(g, blk, [=] { skinny_reduce_kernel<false, false>(r); });
-    return 0;
+    return emu_skinny_rows(SkinnyArgs{(const bf16_t*)A, (const bf16_t*)W, nullptr, M, N, K, lda, ldw, 0, 0}, gemm_skinny_kernel<1>, gemm_skinny_kernel<2>,
+                           gemm_skinny_kernel<4>, nullptr, C, bias, res, ldc, ldres, flags);
+}
+extern "C" int32_t vl2_gemm_skinny_fp8(const void* A, const void* q, const float* scale, void* C, const float* bias, const void* res, int32_t M,
+                                       int32_t N, int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws,
+                                       int64_t ws_bytes, void*) {
+    if (!ws || ws_bytes <= 0 || !scale) return -1;
+    return emu_skinny_rows(Skinny8Args{(const bf16_t*)A, (const uint8_t*)q, nullptr, M, N, K, lda, ldq, 0, 0}, gemm_skinny_fp8_kernel<1>,
+                           gemm_skinny_fp8_kernel<2>, gemm_skinny_fp8_kernel<4>, scale, C, bias, res, ldc, ldres, flags);
 }
 extern "C" int32_t vl2_gemv_batched_bf16(const void* W, const void* x, const float* norm_w, const void* res, const float* bias,
                                          void* y, int32_t MB, int32_t N, int32_t K, int32_t ldw, int32_t ldx, int32_t ldy,

@@ -1055,6 +1055,63 @@ def test_emu_gemm_skinny_all_epilogues(emu):
     assert rel(ops.gemm_skinny(a, pack_gate_up(wg, wu), swiglu=True), ref) < TOL_BF16_OUT
 
 
+def _fp8_dequant(q, scale):
+    """e4m3fn bytes x power-of-two row scales -> the 16-bit weights they stand for (exact in bf16)"""
+    return (q.view(torch.float8_e4m3fn).float() * scale[:, None]).to(torch.bfloat16)
+
+
+def test_emu_gemm_skinny_fp8_equals_skinny_on_the_dequantised_weights(emu):
+    """One skinny body behind both weight formats and one plan from N and K only: the fp8 output is gemm_skinny's on the dequantised weights
+    bit for bit (mt = 1, 2, 4; every epilogue), and a row's bits do not depend on the other rows of the batch."""
+    from videollama2_amd import ops
+    from videollama2_amd.weights import pack_gate_up
+    for M, N, K in ((5, 128, 192), (16, 64, 64), (23, 192, 384), (64, 128, 256), (33, 64, 96)):
+        a, w, bias, res = bf(M, K), bf(N, K, scale=K ** -0.5), torch.randn(N), bf(M, N)
+        q, sc = ops.quant_fp8(w)
+        wd = _fp8_dequant(q, sc)
+        for kw in (dict(), dict(out_f32=True), dict(bias=bias), dict(res=res), dict(bias=bias, res=res, out_f32=True)):
+            got = ops.gemm_skinny_fp8(a, q, sc, **kw)
+            assert torch.equal(got, ops.gemm_skinny(a, wd, **kw)), (M, N, K, sorted(kw))
+            for m in (1, M // 2 + 1):                                         # fewer rows (another mt where M > 16): the same bits per row
+                sub = {k: (v[:m] if k == "res" else v) for k, v in kw.items()}
+                assert torch.equal(ops.gemm_skinny_fp8(a[:m], q, sc, **sub), got[:m]), (M, N, K, m, sorted(kw))
+    for M in (7, 19, 40):
+        a, res = bf(M, 256), bf(M, 128)
+        wgu = pack_gate_up(bf(128, 256, scale=1 / 16), bf(128, 256, scale=1 / 16, seed=1))
+        q, sc = ops.quant_fp8(wgu)
+        got = ops.gemm_skinny_fp8(a, q, sc, swiglu=True, res=res)
+        assert torch.equal(got, ops.gemm_skinny(a, _fp8_dequant(q, sc), swiglu=True, res=res)), M
+        assert torch.equal(ops.gemm_skinny_fp8(a[:3], q, sc, swiglu=True, res=res[:3]), got[:3]), M
+
+
+def test_emu_gemv_batched_fp8_rows_equal_the_single_row_gemv(emu):
+    """One fp8 GEMV body, MB a parameter: every row of a batched call (MB = 1..4 per launch, and a batch that is split) equals the single-row
+    call bit for bit -- fused RMSNorm (weighted and plain), bias, residual, fp32 output, SwiGLU; strided rows; both NP forms (K <= 4096 / longer)."""
+    from videollama2_amd import ops
+    from videollama2_amd.weights import pack_gate_up
+    for K, N in ((512, 192), (4352, 8)):
+        xbuf = bf(6, K + 64)                      # strided rows
+        w, nw, bias, resb = bf(N, K, scale=K ** -0.5), 1 + 0.1 * torch.randn(K), torch.randn(N), bf(6, N)
+        q, sc = ops.quant_fp8(w)
+        for MB in (1, 2, 3, 4, 6):
+            x, res = xbuf[:MB, :K], resb[:MB]
+            for kw in (dict(), dict(norm_w=nw, eps=1e-5), dict(rms_plain=True), dict(bias=bias, res=True), dict(norm_w=nw, out_f32=True)):
+                kw = dict(kw)
+                use_res = kw.pop("res", False)
+                got = ops.gemv_batched_fp8(q, sc, x, res=res if use_res else None, **kw)
+                for b in range(MB):
+                    one = ops.gemv_fp8(q, sc, x[b].contiguous(), res=res[b].contiguous() if use_res else None, **kw)
+                    assert torch.equal(got[b], one), (K, MB, sorted(kw), b)
+    K = 512
+    x, res = bf(5, K), bf(5, 128)
+    q, sc = ops.quant_fp8(pack_gate_up(bf(128, K, scale=K ** -0.5), bf(128, K, scale=K ** -0.5, seed=1)))
+    nw = 1 + 0.1 * torch.randn(K)
+    for MB in (1, 2, 3, 4, 5):
+        got = ops.gemv_batched_fp8(q, sc, x[:MB], norm_w=nw, swiglu=True, res=res[:MB])
+        for b in range(MB):
+            assert torch.equal(got[b], ops.gemv_fp8(q, sc, x[b].contiguous(), norm_w=nw, swiglu=True, res=res[b].contiguous())), (MB, b)
+
+
 def test_emu_kv_cache_limits(emu, golden_small):
     """Maximum sizes: a prompt longer than the KV cache is refused, generation stops when the cache is full (the last token
     is produced from the logits of the last cache row), and a sequence that exactly fills the cache still prefills."""

@@ -65,6 +65,106 @@ __global__ __launch_bounds__(256) void rope_kv_kernel(const bf16_t* __restrict__
     }
 }
 
+// ---- THE x prologue of the decode GEMVs (16-bit, fp8 and MXFP4 weights, single-row and multi-row): MB rows of x [MB, ldx] -> LDS xs [MB][K]
+// in the 16-bit element type, optionally RMS-normalised (HF MistralRMSNorm: fp32 statistics, (x * rstd) * w rounded to 16 bits; rms_plain = the
+// weight vector is folded into W: (v * rstd) * 1 == v * rstd, the same bits).  The decode step's central guarantee hangs on the staged x being
+// the SAME bits in every kernel -- a row of a batched step == the single-sequence step, a quantised step == the 16-bit kernels on the
+// dequantised weights -- and that now holds because this is the only copy.  Under -ffast-math two instantiations were free to associate
+// "v * rstd * w" and the sum of squares differently (seen on hardware: one logit row in thousands off by 3e-4), hence the fixed order and the
+// explicit FMAs: 256 threads x (k, k + 2048, ...), wave sums, (w0 + w1) + (w2 + w3).  256 threads; contains two workgroup barriers.
+template <int MB>
+__device__ __forceinline__ void gemv_stage_x(const bf16_t* x, int ldx, const float* norm_w, int rms_plain, int K, float eps, bf16_t* xs,
+                                             float (&red)[MB][4]) {
+#pragma clang fp reassociate(off)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float rstd[MB];
+#pragma unroll
+    for (int b = 0; b < MB; ++b) rstd[b] = 1.f;
+    const bool norm = norm_w != nullptr || rms_plain;
+    if (norm) {
+#pragma unroll
+        for (int b = 0; b < MB; ++b) {
+            float ss = 0.f;
+            for (int k = tid * 8; k < K; k += 2048) {
+                float v[8];
+                unpack8(*(const u32x4*)(x + (size_t)b * ldx + k), v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) red[b][wave] = ss;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < MB; ++b) rstd[b] = rsqrtf(((red[b][0] + red[b][1]) + (red[b][2] + red[b][3])) / (float)K + eps);
+    }
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+        for (int k = tid * 8; k < K; k += 2048) {
+            u32x4 raw = *(const u32x4*)(x + (size_t)b * ldx + k);
+            if (norm) {
+                float v[8];
+                unpack8(raw, v);
+                f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
+                if (norm_w) { w0 = *(const f32x4*)(norm_w + k); w1 = *(const f32x4*)(norm_w + k + 4); }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd[b]) * (j < 4 ? w0[j] : w1[j - 4]);
+                raw = pack8(v);                      // HF: the norm's output is a 16-bit tensor
+            }
+            *(u32x4*)(xs + (size_t)b * K + k) = raw;
+        }
+    __syncthreads();
+}
+
+// ---- the epilogues (the fp pragma as in gemv_stage_x: the kernels that inline them must agree to the bit).
+// 16-bit weights, one output j of row b of the batch (lane 0, after the wave sums): SwiGLU pairing, bias, residual, store.
+template <bool SWIGLU, bool OUT_F32>
+__device__ __forceinline__ void gemv_store_one(float a0, float a1, int j, const float* bias, const bf16_t* res, void* y, size_t yo) {
+#pragma clang fp reassociate(off)
+    float o = SWIGLU ? silu_f(a0) * a1 : a0;
+    if (!SWIGLU && bias) o += bias[j];
+    if (res) o += bf2f(res[j]);
+    if (OUT_F32) ((float*)y)[yo + j] = o;
+    else ((bf16_t*)y)[yo + j] = f2bf(o);
+}
+// Quantised weights: a wave owns PAIRS of weight rows.  Pair jp = (gate jp, up jp) of a packed 64-row block -> one output with SWIGLU, rows
+// (2 jp, 2 jp + 1) -> two outputs without.
+template <bool SWIGLU>
+__device__ __forceinline__ void gemv_pair_rows(int jp, int& r0, int& r1) {
+    r0 = SWIGLU ? (jp >> 5) * 64 + (jp & 31) : 2 * jp;
+    r1 = SWIGLU ? r0 + 32 : r0 + 1;
+}
+// the whole wave: the MB rows' wave sums of pair jp, then in lane 0 the row scale (SCALED: one fp32 per weight row multiplies the sum; the
+// formats whose scale rides in the conversion pass false), SwiGLU pairing, bias, residual and the 16-bit / fp32 store
+template <bool SWIGLU, bool OUT_F32, bool SCALED, int MB>
+__device__ __forceinline__ void gemv_store_pair(const float (&a0)[MB], const float (&a1)[MB], int jp, const float* scale, const float* bias,
+                                                const bf16_t* res0, int ldres, void* y, int ldy) {
+#pragma clang fp reassociate(off)
+    int r0, r1;
+    gemv_pair_rows<SWIGLU>(jp, r0, r1);
+    float s0[MB], s1[MB];
+#pragma unroll
+    for (int b = 0; b < MB; ++b) { s0[b] = wave_sum(a0[b]); s1[b] = wave_sum(a1[b]); }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int b = 0; b < MB; ++b) {
+            float t0 = s0[b], t1 = s1[b];
+            if (SCALED) { t0 *= scale[r0]; t1 *= scale[r1]; }
+            const bf16_t* res = res0 ? res0 + (size_t)b * ldres : nullptr;
+            if (SWIGLU) {
+                float o = silu_f(t0) * t1;
+                if (res) o += bf2f(res[jp]);
+                ((bf16_t*)y)[(size_t)b * ldy + jp] = f2bf(o);
+            } else {
+                if (bias) { t0 += bias[r0]; t1 += bias[r1]; }
+                if (res) { t0 += bf2f(res[r0]); t1 += bf2f(res[r1]); }
+                if (OUT_F32) { ((float*)y)[(size_t)b * ldy + r0] = t0; ((float*)y)[(size_t)b * ldy + r1] = t1; }
+                else { ((bf16_t*)y)[(size_t)b * ldy + r0] = f2bf(t0); ((bf16_t*)y)[(size_t)b * ldy + r1] = f2bf(t1); }
+            }
+        }
+    }
+}
+
 struct GemvArgs {
     const bf16_t* W;        // [N, ldw]  (SWIGLU: packed blocks of 64 rows = 32 gate rows then 32 up rows)
     const bf16_t* x;        // [K]
@@ -82,12 +182,8 @@ struct GemvArgs {
 // (the body takes the workgroup index so that k_moe.h can run it on an expert's rows chosen on the device)
 template <bool SWIGLU, bool OUT_F32, int RPW>
 __device__ __forceinline__ void gemv_bf16_body(const GemvArgs& p, int bid) {
-    // The fused RMSNorm must give the SAME bits here and in gemv_mr_bf16_kernel (a row of a batched decode step == the
-    // single-sequence step): under -ffast-math the two instantiations were free to associate "v * rstd * w" and the
-    // sum of squares differently (seen on hardware: one logit row in thousands off by 3e-4).  Fixed order, explicit FMAs.
-#pragma clang fp reassociate(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    __shared__ float red[8];
+    __shared__ float red[1][4];
     bf16_t* xs = (bf16_t*)vl2_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_out = SWIGLU ? p.N / 2 : p.N;
@@ -112,36 +208,7 @@ __device__ __forceinline__ void gemv_bf16_body(const GemvArgs& p, int bid) {
     };
     const int jfirst = (bid * 4 + wave) * RPW;
     if (one_pass && jfirst < n_out) issue_row(jfirst, 0);
-    // stage x (optionally RMS-normalised: HF MistralRMSNorm, fp32 statistics, result rounded to bf16)
-    float rstd = 1.f;
-    const bool norm = p.norm_w != nullptr || p.rms_plain;
-    if (norm) {
-        float ss = 0.f;
-        for (int k = tid * 8; k < p.K; k += 2048) {
-            float v[8];
-            unpack8(*(const u32x4*)(p.x + k), v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) red[wave] = ss;
-        __syncthreads();
-        rstd = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)p.K + p.eps);
-    }
-    for (int k = tid * 8; k < p.K; k += 2048) {
-        u32x4 raw = *(const u32x4*)(p.x + k);
-        if (norm) {
-            float v[8];
-            unpack8(raw, v);
-            f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
-            if (p.norm_w) { w0 = *(const f32x4*)(p.norm_w + k); w1 = *(const f32x4*)(p.norm_w + k + 4); }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd) * (j < 4 ? w0[j] : w1[j - 4]);
-            raw = pack8(v);
-        }
-        *(u32x4*)(xs + k) = raw;
-    }
-    __syncthreads();
+    gemv_stage_x<1>(p.x, 0, p.norm_w, p.rms_plain, p.K, p.eps, xs, red);
 
 #pragma unroll 1
     for (int r = 0; r < RPW; ++r) {
@@ -165,13 +232,7 @@ __device__ __forceinline__ void gemv_bf16_body(const GemvArgs& p, int bid) {
         }
         a0 = wave_sum(a0);
         if (SWIGLU) a1 = wave_sum(a1);
-        if (lane == 0) {
-            float o = SWIGLU ? silu_f(a0) * a1 : a0;
-            if (!SWIGLU && p.bias) o += p.bias[j];
-            if (p.res) o += bf2f(p.res[j]);
-            if (OUT_F32) ((float*)p.y)[j] = o;
-            else ((bf16_t*)p.y)[j] = f2bf(o);
-        }
+        if (lane == 0) gemv_store_one<SWIGLU, OUT_F32>(a0, a1, j, p.bias, p.res, p.y, 0);
     }
 }
 
@@ -188,7 +249,9 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
 // XV = 16-B vectors of x per thread (K <= XV * 2048).  grid = ceil(N_out / 4), block 256, dynamic LDS = K * 2 bytes.
 template <bool SWIGLU, bool OUT_F32, int XV>
 __global__ __launch_bounds__(256) void gemv_xfirst_bf16_kernel(GemvArgs p) {
-#pragma clang fp reassociate(off)                  // see gemv_bf16_kernel: the norm arithmetic is pinned to one order
+    // x arrives in REGISTERS here, so this prologue is gemv_stage_x's arithmetic restated (the only restatement left): the same FMAs, combine
+    // and (v * rstd) * w in the same order, pinned by the same pragma
+#pragma clang fp reassociate(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
     __shared__ float red[8];
     bf16_t* xs = (bf16_t*)vl2_smem;
@@ -273,13 +336,7 @@ __global__ __launch_bounds__(256) void gemv_xfirst_bf16_kernel(GemvArgs p) {
     }
     a0 = wave_sum(a0);
     if (SWIGLU) a1 = wave_sum(a1);
-    if (lane == 0) {
-        float o = SWIGLU ? silu_f(a0) * a1 : a0;
-        if (!SWIGLU && p.bias) o += p.bias[j];
-        if (p.res) o += bf2f(p.res[j]);
-        if (OUT_F32) ((float*)p.y)[j] = o;
-        else ((bf16_t*)p.y)[j] = f2bf(o);
-    }
+    if (lane == 0) gemv_store_one<SWIGLU, OUT_F32>(a0, a1, j, p.bias, p.res, p.y, 0);
 }
 
 // Multi-row form for BATCHED decode: y[b][:] = W x[b][:] for MB = 2..4 sequences in one pass over W.
@@ -289,7 +346,6 @@ __global__ __launch_bounds__(256) void gemv_xfirst_bf16_kernel(GemvArgs p) {
 // vector is multiplied against the MB x vectors it meets.  grid = ceil(N_out / 4), block 256.
 template <bool SWIGLU, bool OUT_F32, int MB, int RPW>
 __global__ __launch_bounds__(256) void gemv_mr_bf16_kernel(GemvArgs p) {
-#pragma clang fp reassociate(off)                  // see gemv_bf16_kernel: the norm arithmetic is pinned to one order
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
     __shared__ float red[MB][4];
     bf16_t* xs = (bf16_t*)vl2_smem;
@@ -313,41 +369,7 @@ __global__ __launch_bounds__(256) void gemv_mr_bf16_kernel(GemvArgs p) {
     };
     const int jfirst = (blockIdx.x * 4 + wave) * RPW;      // RPW consecutive output rows per wave: staging MB rows of x
     if (one_pass && jfirst < n_out) issue_row(jfirst, 0);  // (MB x the single-row prologue) is amortised over 4*RPW rows
-    float rstd[MB];
-#pragma unroll
-    for (int b = 0; b < MB; ++b) rstd[b] = 1.f;
-    if (p.norm_w) {
-#pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            float ss = 0.f;
-            for (int k = tid * 8; k < p.K; k += 2048) {
-                float v[8];
-                unpack8(*(const u32x4*)(p.x + (size_t)b * p.ldx + k), v);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) ss = __builtin_fmaf(v[q], v[q], ss);
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) red[b][wave] = ss;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < MB; ++b) rstd[b] = rsqrtf(((red[b][0] + red[b][1]) + (red[b][2] + red[b][3])) / (float)p.K + p.eps);
-    }
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-        for (int k = tid * 8; k < p.K; k += 2048) {
-            u32x4 raw = *(const u32x4*)(p.x + (size_t)b * p.ldx + k);
-            if (p.norm_w) {
-                float v[8];
-                unpack8(raw, v);
-                const f32x4 w0 = *(const f32x4*)(p.norm_w + k), w1 = *(const f32x4*)(p.norm_w + k + 4);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = (v[q] * rstd[b]) * (q < 4 ? w0[q] : w1[q - 4]);
-                raw = pack8(v);
-            }
-            *(u32x4*)(xs + (size_t)b * p.K + k) = raw;
-        }
-    __syncthreads();
+    gemv_stage_x<MB>(p.x, p.ldx, p.norm_w, 0, p.K, p.eps, xs, red);      // (the batched 16-bit entry has no rms_plain form)
 #pragma unroll 1
     for (int r = 0; r < RPW; ++r) {
     const int j = jfirst + r;
@@ -380,13 +402,8 @@ __global__ __launch_bounds__(256) void gemv_mr_bf16_kernel(GemvArgs p) {
     }
     if (lane == 0) {
 #pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            float o = SWIGLU ? silu_f(a0[b]) * a1[b] : a0[b];
-            if (!SWIGLU && p.bias) o += p.bias[j];
-            if (p.res) o += bf2f(p.res[(size_t)b * p.ldres + j]);
-            if (OUT_F32) ((float*)p.y)[(size_t)b * p.ldy + j] = o;
-            else ((bf16_t*)p.y)[(size_t)b * p.ldy + j] = f2bf(o);
-        }
+        for (int b = 0; b < MB; ++b)
+            gemv_store_one<SWIGLU, OUT_F32>(a0[b], a1[b], j, p.bias, p.res ? p.res + (size_t)b * p.ldres : nullptr, p.y, (size_t)b * p.ldy);
     }
     }
 }

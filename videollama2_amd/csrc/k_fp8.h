@@ -9,8 +9,9 @@
 //                           power of two, as the hardware's own MX block scales are: applying and removing it is EXACT, so the quantiser is
 //                           reproducible bit for bit on any machine -- no division, whose fast-math lowering on the GPU is a reciprocal);
 //                           q = RNE_e4m3fn(w * 2^-e).  A zero (or denormal-only) row gets scale 1.
-//   gemv_fp8_kernel       : y = scale * (q x) (+ bias) (+ res) for one token; fused RMSNorm prologue, SwiGLU pairing and residual epilogue
-//                           as gemv_bf16_kernel (k_decode.h), x staged in LDS in the 16-bit element type exactly as there
+//   gemv_fp8_kernel       : y = scale * (q x) (+ bias) (+ res) for one token; the fused RMSNorm prologue of gemv_bf16_kernel (k_decode.h
+//                           gemv_stage_x: x staged in LDS in the 16-bit element type), SwiGLU pairing and residual epilogue
+//   gemv_mr_fp8_kernel    : 2..4 rows of x in one pass over q, every row bit for bit the single-row kernel (ONE body, MB a parameter)
 #pragma once
 #include "k_decode.h"
 
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void quant_act_fp8_kernel(const bf16_t* __rest
 struct Gemv8Args {
     const uint8_t* W;       // [N, ldw] e4m3fn bytes (SWIGLU: packed blocks of 64 rows = 32 gate rows then 32 up rows, like the 16-bit layout)
     const float* scale;     // [N] one per (packed) row
-    const bf16_t* x;        // [K]
+    const bf16_t* x;        // [K] (row 0 of [MB, ldx])
     const float* norm_w;    // fused RMSNorm prologue on x (or null)
     const bf16_t* res;      // [N_out] residual (or null)
     void* y;                // 16-bit or fp32 [N_out]
@@ -118,19 +119,24 @@ struct Gemv8Args {
     float eps;
     const float* bias;      // [N_out] or null; not with SWIGLU
     int rms_plain;          // RMS-normalise x without a weight vector (folded into W before quantisation)
+    int ldx, ldy, ldres;    // element strides between the rows of x / y / res (MB > 1)
 };
 
+// ONE body, MB = rows of x per pass a parameter: gemv_fp8_kernel is MB = 1, gemv_mr_fp8_kernel MB = 2..4 (batched decode: y[b][:] = scale *
+// (q x[b]) (+ bias) (+ res[b]) in one pass over q -- what gemv_mr_bf16_kernel is to gemv_bf16_kernel).
 // A wave owns NP PAIRS of weight rows per trip and keeps all their loads in flight: 8 x 16 B per lane and row array = 16 KiB per wave,
 // the 16-bit kernel's SwiGLU footprint -- the stream is bound by bytes in flight, so rows of K <= 4096 (four 16-B vectors per lane) run
-// two pairs at a time (NP = 2), longer rows one.  A pair = (gate j, up j) -> one output with SWIGLU, rows (2 jp, 2 jp + 1) -> two outputs
-// without (N even).  x lives in LDS in the 16-bit element type exactly as gemv_bf16_kernel stages it; a weight dword becomes two packed
-// element pairs (v_cvt_pk_f32_fp8 + the pack: every e4m3fn value is exact in bf16 and in half) and meets x in v_dot2: fp32 sums.
-// grid = ceil(n_pairs / (4 NP)), block 256; dynamic LDS = K * 2 bytes.  K % 16 == 0, K <= 32704; NP = 2 needs K <= 4096.
-template <bool SWIGLU, bool OUT_F32, int NP>
-__global__ __launch_bounds__(256) void gemv_fp8_kernel(Gemv8Args p) {
-#pragma clang fp reassociate(off)                  // the RMSNorm arithmetic in gemv_bf16_kernel's order: the staged x is the same bits
+// two pairs at a time (NP = 2), longer rows one.  Pairs: gemv_pair_rows (N even).  x lives in LDS in the 16-bit element type as [MB][K], staged
+// by gemv_stage_x; a weight dword becomes two packed element pairs ONCE (v_cvt_pk_f32_fp8 + the pack: every e4m3fn value is exact in bf16 and
+// in half) and meets the MB x vectors it serves in v_dot2: fp32 sums.  Each row's sum takes its products in the same order -- the per-lane
+// walk over the 16-B weight vectors (lane, lane + 64, ...), the dot2 sequence per pair row -- whatever NP and MB are, and the prologue and
+// epilogue are the shared ones, so a row of the multi-row form is the single-row form bit for bit.
+// grid = ceil(n_pairs / (4 NP)), block 256; dynamic LDS = MB * K * 2 bytes (<= 64 KiB: the launcher splits larger batches).
+// K % 16 == 0, K <= 32704; NP = 2 needs K <= 4096.
+template <bool SWIGLU, bool OUT_F32, int NP, int MB>
+__device__ __forceinline__ void gemv_fp8_body(const Gemv8Args& p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    __shared__ float red[8];
+    __shared__ float red[MB][4];
     bf16_t* xs = (bf16_t*)vl2_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_pairs = p.N / 2;
@@ -139,15 +145,11 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(Gemv8Args p) {
     const bool one_pass = nvec <= 64 * SL;
     u32x4 wv[8], uv[8];
     const int jp0 = (blockIdx.x * 4 + wave) * NP;    // this wave's first pair
-    auto rows_of = [&](int jp, int& r0, int& r1) {
-        r0 = SWIGLU ? (jp >> 5) * 64 + (jp & 31) : 2 * jp;
-        r1 = SWIGLU ? r0 + 32 : r0 + 1;
-    };
     auto issue_rows = [&](int v0) {
 #pragma unroll
         for (int pr = 0; pr < NP; ++pr) {
             int r0, r1;
-            rows_of(jp0 + pr, r0, r1);
+            gemv_pair_rows<SWIGLU>(jp0 + pr, r0, r1);
             const uint8_t* w0p = p.W + (size_t)r0 * p.ldw;
             const uint8_t* w1p = p.W + (size_t)r1 * p.ldw;
             const bool live = jp0 + pr < n_pairs;
@@ -162,171 +164,7 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(Gemv8Args p) {
         }
     };
     if (one_pass && jp0 < n_pairs) issue_rows(0);    // the weights do not depend on x: their latency overlaps the staging of x
-    float rstd = 1.f;
-    const bool norm = p.norm_w != nullptr || p.rms_plain;
-    if (norm) {
-        float ss = 0.f;
-        for (int k = tid * 8; k < p.K; k += 2048) {
-            float v[8];
-            unpack8(*(const u32x4*)(p.x + k), v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
-        }
-        ss = wave_sum(ss);
-        if (lane == 0) red[wave] = ss;
-        __syncthreads();
-        rstd = rsqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)p.K + p.eps);
-    }
-    for (int k = tid * 8; k < p.K; k += 2048) {
-        u32x4 raw = *(const u32x4*)(p.x + k);
-        if (norm) {
-            float v[8];
-            unpack8(raw, v);
-            f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
-            if (p.norm_w) { w0 = *(const f32x4*)(p.norm_w + k); w1 = *(const f32x4*)(p.norm_w + k + 4); }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd) * (j < 4 ? w0[j] : w1[j - 4]);
-            raw = pack8(v);                          // HF: the norm's output is a 16-bit tensor
-        }
-        *(u32x4*)(xs + k) = raw;
-    }
-    __syncthreads();
-    if (jp0 >= n_pairs) return;
-    float a0[NP], a1[NP];
-#pragma unroll
-    for (int pr = 0; pr < NP; ++pr) a0[pr] = a1[pr] = 0.f;
-    for (int v0 = 0; v0 < nvec; v0 += 64 * SL) {
-        if (!one_pass) issue_rows(v0);
-#pragma unroll
-        for (int pr = 0; pr < NP; ++pr) {
-            if (jp0 + pr >= n_pairs) continue;
-#pragma unroll
-            for (int i = 0; i < SL; ++i) {
-                const int v = v0 + i * 64 + lane;
-                if (v < nvec) {
-                    const u32x4 x0 = *(const u32x4*)(xs + (size_t)v * 16), x1 = *(const u32x4*)(xs + (size_t)v * 16 + 8);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const unsigned xl = q < 2 ? x0[2 * q] : x1[2 * q - 4], xh = q < 2 ? x0[2 * q + 1] : x1[2 * q - 3];
-                        const vl2_f32x2_t w0l = VL2_CVT_PK_F32_FP8(wv[pr * SL + i][q], false), w0h = VL2_CVT_PK_F32_FP8(wv[pr * SL + i][q], true);
-                        const vl2_f32x2_t w1l = VL2_CVT_PK_F32_FP8(uv[pr * SL + i][q], false), w1h = VL2_CVT_PK_F32_FP8(uv[pr * SL + i][q], true);
-                        a0[pr] = dot2_bf16(pack2bf(w0l[0], w0l[1]), xl, a0[pr]);
-                        a1[pr] = dot2_bf16(pack2bf(w1l[0], w1l[1]), xl, a1[pr]);
-                        a0[pr] = dot2_bf16(pack2bf(w0h[0], w0h[1]), xh, a0[pr]);
-                        a1[pr] = dot2_bf16(pack2bf(w1h[0], w1h[1]), xh, a1[pr]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int pr = 0; pr < NP; ++pr) {
-        const int jp = jp0 + pr;
-        if (jp >= n_pairs) continue;
-        int r0, r1;
-        rows_of(jp, r0, r1);
-        float s0 = wave_sum(a0[pr]), s1 = wave_sum(a1[pr]);
-        if (lane == 0) {
-            s0 *= p.scale[r0];
-            s1 *= p.scale[r1];
-            if (SWIGLU) {
-                float o = silu_f(s0) * s1;
-                if (p.res) o += bf2f(p.res[jp]);
-                ((bf16_t*)p.y)[jp] = f2bf(o);
-            } else {
-                if (p.bias) { s0 += p.bias[r0]; s1 += p.bias[r1]; }
-                if (p.res) { s0 += bf2f(p.res[r0]); s1 += bf2f(p.res[r1]); }
-                if (OUT_F32) { ((float*)p.y)[r0] = s0; ((float*)p.y)[r1] = s1; }
-                else { ((bf16_t*)p.y)[r0] = f2bf(s0); ((bf16_t*)p.y)[r1] = f2bf(s1); }
-            }
-        }
-    }
-}
-
-// Multi-row form for BATCHED decode on the fp8 weights: y[b][:] = scale * (q x[b]) (+ bias) (+ res[b]) for MB = 2..4 sequences in one pass over
-// q -- what gemv_mr_bf16_kernel is to gemv_bf16_kernel.  Every row is gemv_fp8_kernel on that row, bit for bit: the same RMSNorm prologue (per
-// row, the same order), the same per-lane walk over the 16-B weight vectors (lane, lane + 64, ... whatever NP), the same dot2 sequence per pair
-// row, wave reduction, scale, SwiGLU pairing, bias and residual epilogue.  A weight dword is converted to element pairs ONCE and meets the MB x
-// vectors it serves.  x rows live in LDS as [MB][K] (MB * K * 2 <= 64 KiB: the launcher splits larger batches).  grid and NP as gemv_fp8_kernel.
-struct Gemv8MrArgs {
-    Gemv8Args g;            // W, scale, x (row 0), norm_w, res (row 0), y (row 0), N, K, ldw, eps, bias, rms_plain
-    int ldx, ldy, ldres;    // element strides between the rows of x / y / res
-};
-
-template <bool SWIGLU, bool OUT_F32, int NP, int MB>
-__global__ __launch_bounds__(256) void gemv_mr_fp8_kernel(Gemv8MrArgs pa) {
-#pragma clang fp reassociate(off)                  // the RMSNorm arithmetic in gemv_fp8_kernel's order
-    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    __shared__ float red[MB][4];
-    const Gemv8Args& p = pa.g;
-    bf16_t* xs = (bf16_t*)vl2_smem;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_pairs = p.N / 2;
-    const int nvec = p.K >> 4;
-    constexpr int SL = 8 / NP;
-    const bool one_pass = nvec <= 64 * SL;
-    u32x4 wv[8], uv[8];
-    const int jp0 = (blockIdx.x * 4 + wave) * NP;
-    auto rows_of = [&](int jp, int& r0, int& r1) {
-        r0 = SWIGLU ? (jp >> 5) * 64 + (jp & 31) : 2 * jp;
-        r1 = SWIGLU ? r0 + 32 : r0 + 1;
-    };
-    auto issue_rows = [&](int v0) {
-#pragma unroll
-        for (int pr = 0; pr < NP; ++pr) {
-            int r0, r1;
-            rows_of(jp0 + pr, r0, r1);
-            const uint8_t* w0p = p.W + (size_t)r0 * p.ldw;
-            const uint8_t* w1p = p.W + (size_t)r1 * p.ldw;
-            const bool live = jp0 + pr < n_pairs;
-#pragma unroll
-            for (int i = 0; i < SL; ++i) {
-                const int v = v0 + i * 64 + lane;
-                if (live && v < nvec) {
-                    wv[pr * SL + i] = __builtin_nontemporal_load((const u32x4*)(w0p + (size_t)v * 16));
-                    uv[pr * SL + i] = __builtin_nontemporal_load((const u32x4*)(w1p + (size_t)v * 16));
-                }
-            }
-        }
-    };
-    if (one_pass && jp0 < n_pairs) issue_rows(0);
-    float rstd[MB];
-#pragma unroll
-    for (int b = 0; b < MB; ++b) rstd[b] = 1.f;
-    const bool norm = p.norm_w != nullptr || p.rms_plain;
-    if (norm) {
-#pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            float ss = 0.f;
-            for (int k = tid * 8; k < p.K; k += 2048) {
-                float v[8];
-                unpack8(*(const u32x4*)(p.x + (size_t)b * pa.ldx + k), v);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) red[b][wave] = ss;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < MB; ++b) rstd[b] = rsqrtf(((red[b][0] + red[b][1]) + (red[b][2] + red[b][3])) / (float)p.K + p.eps);
-    }
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-        for (int k = tid * 8; k < p.K; k += 2048) {
-            u32x4 raw = *(const u32x4*)(p.x + (size_t)b * pa.ldx + k);
-            if (norm) {
-                float v[8];
-                unpack8(raw, v);
-                f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
-                if (p.norm_w) { w0 = *(const f32x4*)(p.norm_w + k); w1 = *(const f32x4*)(p.norm_w + k + 4); }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd[b]) * (j < 4 ? w0[j] : w1[j - 4]);
-                raw = pack8(v);
-            }
-            *(u32x4*)(xs + (size_t)b * p.K + k) = raw;
-        }
-    __syncthreads();
+    gemv_stage_x<MB>(p.x, p.ldx, p.norm_w, p.rms_plain, p.K, p.eps, xs, red);
     if (jp0 >= n_pairs) return;
     float a0[NP][MB], a1[NP][MB];
 #pragma unroll
@@ -362,30 +200,12 @@ __global__ __launch_bounds__(256) void gemv_mr_fp8_kernel(Gemv8MrArgs pa) {
         }
     }
 #pragma unroll
-    for (int pr = 0; pr < NP; ++pr) {
-        const int jp = jp0 + pr;
-        if (jp >= n_pairs) continue;
-        int r0, r1;
-        rows_of(jp, r0, r1);
-        float s0[MB], s1[MB];
-#pragma unroll
-        for (int b = 0; b < MB; ++b) { s0[b] = wave_sum(a0[pr][b]); s1[b] = wave_sum(a1[pr][b]); }
-        if (lane == 0) {
-#pragma unroll
-            for (int b = 0; b < MB; ++b) {
-                float t0 = s0[b] * p.scale[r0], t1 = s1[b] * p.scale[r1];
-                const bf16_t* res = p.res ? p.res + (size_t)b * pa.ldres : nullptr;
-                if (SWIGLU) {
-                    float o = silu_f(t0) * t1;
-                    if (res) o += bf2f(res[jp]);
-                    ((bf16_t*)p.y)[(size_t)b * pa.ldy + jp] = f2bf(o);
-                } else {
-                    if (p.bias) { t0 += p.bias[r0]; t1 += p.bias[r1]; }
-                    if (res) { t0 += bf2f(res[r0]); t1 += bf2f(res[r1]); }
-                    if (OUT_F32) { ((float*)p.y)[(size_t)b * pa.ldy + r0] = t0; ((float*)p.y)[(size_t)b * pa.ldy + r1] = t1; }
-                    else { ((bf16_t*)p.y)[(size_t)b * pa.ldy + r0] = f2bf(t0); ((bf16_t*)p.y)[(size_t)b * pa.ldy + r1] = f2bf(t1); }
-                }
-            }
-        }
-    }
+    for (int pr = 0; pr < NP; ++pr)
+        if (jp0 + pr < n_pairs) gemv_store_pair<SWIGLU, OUT_F32, true, MB>(a0[pr], a1[pr], jp0 + pr, p.scale, p.bias, p.res, p.ldres, p.y, p.ldy);
 }
+
+template <bool SWIGLU, bool OUT_F32, int NP>
+__global__ __launch_bounds__(256) void gemv_fp8_kernel(Gemv8Args p) { gemv_fp8_body<SWIGLU, OUT_F32, NP, 1>(p); }
+
+template <bool SWIGLU, bool OUT_F32, int NP, int MB>
+__global__ __launch_bounds__(256) void gemv_mr_fp8_kernel(Gemv8Args p) { gemv_fp8_body<SWIGLU, OUT_F32, NP, MB>(p); }

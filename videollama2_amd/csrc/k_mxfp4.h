@@ -10,8 +10,8 @@
 //   quant_mxfp4_rows_kernel  : per block, amax = max|w|, e = floor(log2 amax) - 2 (the exponent field of amax, no log) clamped to [-127, 127],
 //                              0 for a zero block; code = RNE of w * 2^-e onto the E2M1 grid, saturating at +-6 (OCP MX v1.0 section 6.3).
 //                              The scaling is exact and the rounding is seven comparisons: reproducible bit for bit on any machine.
-//   gemv_mxfp4_kernel        : y = W~ x for one token with gemv_fp8_kernel's prologue and epilogue (fused RMSNorm, SwiGLU pairing, bias,
-//                              residual, 16-bit / fp32 output).
+//   gemv_mxfp4_kernel        : y = W~ x for one token with the decode GEMVs' shared prologue and pair epilogue (k_decode.h gemv_stage_x,
+//                              gemv_store_pair: fused RMSNorm, SwiGLU pairing, bias, residual, 16-bit / fp32 output).
 //   gemv_mr_mxfp4_kernel     : 2..4 rows of x in one pass over q, every row bit for bit the single-row kernel (ONE body, MB a parameter).
 //   gemm_skinny_mxfp4_kernel : M <= 64 rows on v_mfma_f32_16x16x32, the twin of gemm_skinny_fp8_kernel.
 //
@@ -96,14 +96,13 @@ struct Gemv4Args {
 
 // One 16-byte load per lane is 32 weights = exactly one scale block, so a lane's vector has ONE scale.  A wave owns NP PAIRS of weight rows per
 // trip and keeps 16 vectors per lane (16 KiB per wave, gemv_fp8_kernel's footprint) in flight: rows of K <= 4096 are two vectors per lane, so
-// NP = 4 (eight rows), longer rows NP = 1.  A pair = (gate j, up j) -> one output with SWIGLU, rows (2 jp, 2 jp + 1) without (N even).
-// x lives in LDS in the 16-bit element type as [MB][K], staged exactly as gemv_fp8_kernel stages it.  Per vector the 2 NP rows' dwords are
+// NP = 4 (eight rows), longer rows NP = 1.  Pairs: gemv_pair_rows (k_decode.h; N even).
+// x lives in LDS in the 16-bit element type as [MB][K], staged by gemv_stage_x like every decode GEMV's.  Per vector the 2 NP rows' dwords are
 // converted once (v_cvt_scalef32_pk_*_fp4, the block scale in the conversion) and every x read from LDS serves all of them; each row's fp32 sum
 // takes its products in k order whatever NP and MB are, so a row of the multi-row form is the single-row form bit for bit.
 // grid = ceil(n_pairs / (4 NP)), block 256; dynamic LDS = MB * K * 2 bytes.  K % 32 == 0, MB * K <= 32704.
 template <bool SWIGLU, bool OUT_F32, int NP, int MB>
 __device__ __forceinline__ void gemv_mxfp4_body(const Gemv4Args& p) {
-#pragma clang fp reassociate(off)                  // the RMSNorm arithmetic in gemv_bf16_kernel's order: the staged x is the same bits
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
     __shared__ float red[MB][4];
     bf16_t* xs = (bf16_t*)vl2_smem;
@@ -115,15 +114,11 @@ __device__ __forceinline__ void gemv_mxfp4_body(const Gemv4Args& p) {
     u32x4 wv[8], uv[8];
     uint32_t ws[8], us[8];
     const int jp0 = (blockIdx.x * 4 + wave) * NP;    // this wave's first pair
-    auto rows_of = [&](int jp, int& r0, int& r1) {
-        r0 = SWIGLU ? (jp >> 5) * 64 + (jp & 31) : 2 * jp;
-        r1 = SWIGLU ? r0 + 32 : r0 + 1;
-    };
     auto issue_rows = [&](int v0) {
 #pragma unroll
         for (int pr = 0; pr < NP; ++pr) {
             int r0, r1;
-            rows_of(jp0 + pr, r0, r1);
+            gemv_pair_rows<SWIGLU>(jp0 + pr, r0, r1);
             const bool live = jp0 + pr < n_pairs;
 #pragma unroll
             for (int i = 0; i < SL; ++i) {
@@ -138,43 +133,7 @@ __device__ __forceinline__ void gemv_mxfp4_body(const Gemv4Args& p) {
         }
     };
     if (one_pass && jp0 < n_pairs) issue_rows(0);    // the weights do not depend on x: their latency overlaps the staging of x
-    float rstd[MB];
-#pragma unroll
-    for (int b = 0; b < MB; ++b) rstd[b] = 1.f;
-    const bool norm = p.norm_w != nullptr || p.rms_plain;
-    if (norm) {
-#pragma unroll
-        for (int b = 0; b < MB; ++b) {
-            float ss = 0.f;
-            for (int k = tid * 8; k < p.K; k += 2048) {
-                float v[8];
-                unpack8(*(const u32x4*)(p.x + (size_t)b * p.ldx + k), v);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(v[j], v[j], ss);
-            }
-            ss = wave_sum(ss);
-            if (lane == 0) red[b][wave] = ss;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < MB; ++b) rstd[b] = rsqrtf(((red[b][0] + red[b][1]) + (red[b][2] + red[b][3])) / (float)p.K + p.eps);
-    }
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-        for (int k = tid * 8; k < p.K; k += 2048) {
-            u32x4 raw = *(const u32x4*)(p.x + (size_t)b * p.ldx + k);
-            if (norm) {
-                float v[8];
-                unpack8(raw, v);
-                f32x4 w0 = {1.f, 1.f, 1.f, 1.f}, w1 = w0;
-                if (p.norm_w) { w0 = *(const f32x4*)(p.norm_w + k); w1 = *(const f32x4*)(p.norm_w + k + 4); }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (v[j] * rstd[b]) * (j < 4 ? w0[j] : w1[j - 4]);
-                raw = pack8(v);                      // HF: the norm's output is a 16-bit tensor
-            }
-            *(u32x4*)(xs + (size_t)b * p.K + k) = raw;
-        }
-    __syncthreads();
+    gemv_stage_x<MB>(p.x, p.ldx, p.norm_w, p.rms_plain, p.K, p.eps, xs, red);
     if (jp0 >= n_pairs) return;
     float a0[NP][MB], a1[NP][MB];
 #pragma unroll
@@ -213,32 +172,8 @@ __device__ __forceinline__ void gemv_mxfp4_body(const Gemv4Args& p) {
         }
     }
 #pragma unroll
-    for (int pr = 0; pr < NP; ++pr) {
-        const int jp = jp0 + pr;
-        if (jp >= n_pairs) continue;
-        int r0, r1;
-        rows_of(jp, r0, r1);
-        float s0[MB], s1[MB];
-#pragma unroll
-        for (int b = 0; b < MB; ++b) { s0[b] = wave_sum(a0[pr][b]); s1[b] = wave_sum(a1[pr][b]); }
-        if (lane == 0) {
-#pragma unroll
-            for (int b = 0; b < MB; ++b) {
-                float t0 = s0[b], t1 = s1[b];
-                const bf16_t* res = p.res ? p.res + (size_t)b * p.ldres : nullptr;
-                if (SWIGLU) {
-                    float o = silu_f(t0) * t1;
-                    if (res) o += bf2f(res[jp]);
-                    ((bf16_t*)p.y)[(size_t)b * p.ldy + jp] = f2bf(o);
-                } else {
-                    if (p.bias) { t0 += p.bias[r0]; t1 += p.bias[r1]; }
-                    if (res) { t0 += bf2f(res[r0]); t1 += bf2f(res[r1]); }
-                    if (OUT_F32) { ((float*)p.y)[(size_t)b * p.ldy + r0] = t0; ((float*)p.y)[(size_t)b * p.ldy + r1] = t1; }
-                    else { ((bf16_t*)p.y)[(size_t)b * p.ldy + r0] = f2bf(t0); ((bf16_t*)p.y)[(size_t)b * p.ldy + r1] = f2bf(t1); }
-                }
-            }
-        }
-    }
+    for (int pr = 0; pr < NP; ++pr)
+        if (jp0 + pr < n_pairs) gemv_store_pair<SWIGLU, OUT_F32, false, MB>(a0[pr], a1[pr], jp0 + pr, nullptr, p.bias, p.res, p.ldres, p.y, p.ldy);
 }
 
 template <bool SWIGLU, bool OUT_F32, int NP>
@@ -248,7 +183,8 @@ template <bool SWIGLU, bool OUT_F32, int NP, int MB>
 __global__ __launch_bounds__(256) void gemv_mr_mxfp4_kernel(Gemv4Args p) { gemv_mxfp4_body<SWIGLU, OUT_F32, NP, MB>(p); }
 
 // ---- skinny-M GEMM on the MXFP4 weights (W4A16), 5..64 tokens per step:  C[M <= 64, N] = epilogue( A[M,K] . W~[N,K]^T ).
-// gemm_skinny_kernel's grid, K split, x staging and MFMA sequence WITH ITS LANE-TO-K ASSIGNMENT KEPT: per 32-deep step a lane loads the 4 bytes
+// gemm_skinny_body (k_skinny.h: gemm_skinny_kernel's grid, K split, x staging and MFMA sequence, WITH ITS LANE-TO-K ASSIGNMENT) behind the MXFP4
+// weight policy: per 32-deep step a lane loads the 4 bytes
 // that hold the 8 k of B[k = (lane>>4)*8 + j][n = lane&15] (they lie inside one scale block: one scale byte per load), converts them with the
 // block scale to the element type and feeds v_mfma_f32_16x16x32.  The B operand is therefore the dequantised weight exactly, and the output is
 // bit for bit gemm_skinny_kernel on dequant(q, s) provided the K split is the same -- the launcher picks it from N and K only.  The partials
@@ -262,68 +198,19 @@ struct Skinny4Args {
     int kslice, kchunk;     // K per workgroup (multiple of kchunk), K per LDS chunk (multiple of 32)
 };
 
-// grid = (N/64, KS), block 256; dynamic LDS = Mp * (kchunk + 8) * 2 bytes
-template <int MT>
-__global__ __launch_bounds__(256) void gemm_skinny_mxfp4_kernel(Skinny4Args p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    constexpr int Mp = 16 * MT;
-    constexpr int NL = 16;                                // weight loads in flight per lane
-    bf16_t* xs = (bf16_t*)vl2_smem;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n0 = blockIdx.x * 64 + wave * 16;
-    const int k0 = blockIdx.y * p.kslice;
-    const int pitch = p.kchunk + 8;
-    const int l15 = lane & 15, lg = lane >> 4;
-    const uint8_t* wrow = p.Q + (size_t)(n0 + l15) * p.ldq + (k0 >> 1) + lg * 4;
-    const uint8_t* srow = p.S + (size_t)(n0 + l15) * p.lds + (k0 >> 5);
-
-    f32x4v acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = f32x4v{0.f, 0.f, 0.f, 0.f};
-
-    const int cvec = p.kchunk >> 3;
-    for (int kc = 0; kc < p.kslice; kc += p.kchunk) {
-        const int nstep = p.kchunk >> 5;
-        uint32_t wv[NL], sv[NL];
-#pragma unroll
-        for (int i = 0; i < NL; ++i)
-            if (i < nstep) {
-                wv[i] = __builtin_nontemporal_load((const uint32_t*)(wrow + (kc >> 1) + i * 16));
-                sv[i] = srow[(kc >> 5) + i];
-            }
-        __syncthreads();
-        for (int e = tid; e < Mp * cvec; e += 256) {
-            const int r = e / cvec, c = e - r * cvec;
-            u32x4 v = u32x4{0u, 0u, 0u, 0u};
-            if (r < p.M) v = *(const u32x4*)(p.A + (size_t)r * p.lda + k0 + kc + c * 8);
-            *(u32x4*)(xs + (size_t)r * pitch + c * 8) = v;
-        }
-        __syncthreads();
-        for (int s0 = 0; s0 < nstep; s0 += NL) {
-            if (s0) {
-#pragma unroll
-                for (int i = 0; i < NL; ++i)
-                    if (s0 + i < nstep) {
-                        wv[i] = __builtin_nontemporal_load((const uint32_t*)(wrow + (kc >> 1) + (s0 + i) * 16));
-                        sv[i] = srow[(kc >> 5) + s0 + i];
-                    }
-            }
-#pragma unroll
-            for (int i = 0; i < NL; ++i) {
-                if (s0 + i < nstep) {
-                    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, mx4_cvt8(wv[i], mx4_scale(sv[i])));
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) {
-                        const bf16x8 afrag = *(const bf16x8*)(xs + (size_t)(m * 16 + l15) * pitch + (s0 + i) * 32 + lg * 8);
-                        acc[m] = VL2_MFMA16(afrag, bfrag, acc[m]);
-                    }
-                }
-            }
-        }
+// gemm_skinny_body's policy for the MXFP4 weights: 16 x (4 B of codes + the block's scale byte) in flight per lane
+struct SkinnyWMx4 {
+    using Args = Skinny4Args;
+    static constexpr int NL = 16;
+    struct word { uint32_t q, s; };                       // 8 codes and their block's scale byte
+    const uint8_t *wrow, *srow;
+    __device__ __forceinline__ SkinnyWMx4(const Args& p, int n, int k0, int lg)
+        : wrow(p.Q + (size_t)n * p.ldq + (k0 >> 1) + lg * 4), srow(p.S + (size_t)n * p.lds + (k0 >> 5)) {}
+    __device__ __forceinline__ word load(int kc, int s) const {
+        return word{__builtin_nontemporal_load((const uint32_t*)(wrow + (kc >> 1) + s * 16)), srow[(kc >> 5) + s]};
     }
-    float* dst = p.part + (size_t)blockIdx.y * Mp * p.N;
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[(size_t)(m * 16 + lg * 4 + r) * p.N + n0 + l15] = acc[m][r];
-}
+    static __device__ __forceinline__ bf16x8 frag(word w) { return __builtin_bit_cast(bf16x8, mx4_cvt8(w.q, mx4_scale(w.s))); }
+};
+
+template <int MT>
+__global__ __launch_bounds__(256) void gemm_skinny_mxfp4_kernel(Skinny4Args p) { gemm_skinny_body<MT, SkinnyWMx4>(p); }

@@ -8,6 +8,8 @@
 // all M <= 64 token rows (x chunk in LDS as the A operand).  K is split over gridDim.y workgroups so that ~4096 waves are in
 // flight whatever N is; every workgroup writes its fp32 partial [M, 64] and `skinny_reduce_kernel` sums the slices in order
 // (deterministic) and applies bias / residual / SwiGLU / output conversion.
+// The quantised weight formats stream through the SAME body (gemm_skinny_body) behind a weight-format policy: fp8 in k_skinny_fp8.h, MXFP4 in
+// k_mxfp4.h.
 #pragma once
 #include "dev_common.h"
 
@@ -21,18 +23,34 @@ struct SkinnyArgs {
     int kslice, kchunk;     // K per workgroup (multiple of kchunk), K per LDS chunk (multiple of 32)
 };
 
-// grid = (N/64, KS), block 256; dynamic LDS = Mp * (kchunk + 8) * 2 bytes
-template <int MT>
-__global__ __launch_bounds__(256) void gemm_skinny_kernel(SkinnyArgs p) {
+// The weight-format policy of the 16-bit weights.  A policy WF supplies ONLY what differs between the formats: Args (the kernel's argument
+// struct: A, part, M, N, lda, kslice, kchunk under these names, and the format's own weight fields), the loaded word, NL = loads in flight per
+// lane, the lane's row pointer(s), load(kc, s) = request the word of 32-deep step s of the chunk at kc, and frag(word) = the word as the 8
+// elements k = (lane>>4)*8 + j of B[k][n = lane&15].  Here: 8 x 16 B, and the loaded vector IS the fragment.
+struct SkinnyWBf16 {
+    using Args = SkinnyArgs;
+    static constexpr int NL = 8;
+    using word = u32x4;
+    const bf16_t* wrow;
+    __device__ __forceinline__ SkinnyWBf16(const Args& p, int n, int k0, int lg) : wrow(p.W + (size_t)n * p.ldw + k0 + lg * 8) {}
+    __device__ __forceinline__ word load(int kc, int s) const { return __builtin_nontemporal_load((const u32x4*)(wrow + kc + s * 32)); }
+    static __device__ __forceinline__ bf16x8 frag(word w) { return __builtin_bit_cast(bf16x8, w); }
+};
+
+// THE skinny-M body of every weight format: grid = (N/64, KS), block 256; dynamic LDS = Mp * (kchunk + 8) * 2 bytes.  The grid, the K
+// slicing, the x staging, the MFMA sequence and the partial store exist here only, so two formats whose fragments hold the same values give the
+// same bits (gemm_skinny_fp8_kernel / gemm_skinny_mxfp4_kernel == gemm_skinny_kernel on the dequantised weights, given the same K split).
+template <int MT, class WF>
+__device__ __forceinline__ void gemm_skinny_body(const typename WF::Args& p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    constexpr int Mp = 16 * MT;
+    constexpr int Mp = 16 * MT, NL = WF::NL;
     bf16_t* xs = (bf16_t*)vl2_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.x * 64 + wave * 16;
     const int k0 = blockIdx.y * p.kslice;
     const int pitch = p.kchunk + 8;                       // +16 B per row: the 16 rows of a fragment read hit different banks
     const int l15 = lane & 15, lg = lane >> 4;
-    const bf16_t* wrow = p.W + (size_t)(n0 + l15) * p.ldw + k0 + lg * 8;
+    const WF w(p, n0 + l15, k0, lg);
 
     f32x4v acc[MT];
 #pragma unroll
@@ -41,11 +59,11 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(SkinnyArgs p) {
     const int cvec = p.kchunk >> 3;                       // 16-B vectors per x row per chunk
     for (int kc = 0; kc < p.kslice; kc += p.kchunk) {
         const int nstep = p.kchunk >> 5;                  // 32-deep MFMA steps in this chunk
-        // the chunk's first weight vectors do not depend on x: request them before staging x
-        u32x4 wv[8];
+        // the chunk's first weight words do not depend on x: request them before staging x
+        typename WF::word wv[NL];
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (i < nstep) wv[i] = __builtin_nontemporal_load((const u32x4*)(wrow + kc + i * 32));
+        for (int i = 0; i < NL; ++i)
+            if (i < nstep) wv[i] = w.load(kc, i);
         __syncthreads();                                  // previous chunk's fragment reads are done
         for (int e = tid; e < Mp * cvec; e += 256) {
             const int r = e / cvec, c = e - r * cvec;
@@ -54,16 +72,16 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(SkinnyArgs p) {
             *(u32x4*)(xs + (size_t)r * pitch + c * 8) = v;
         }
         __syncthreads();
-        for (int s0 = 0; s0 < nstep; s0 += 8) {
+        for (int s0 = 0; s0 < nstep; s0 += NL) {
             if (s0) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (s0 + i < nstep) wv[i] = __builtin_nontemporal_load((const u32x4*)(wrow + kc + (s0 + i) * 32));
+                for (int i = 0; i < NL; ++i)
+                    if (s0 + i < nstep) wv[i] = w.load(kc, s0 + i);
             }
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
+            for (int i = 0; i < NL; ++i) {
                 if (s0 + i < nstep) {
-                    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, wv[i]);
+                    const bf16x8 bfrag = WF::frag(wv[i]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         const bf16x8 afrag = *(const bf16x8*)(xs + (size_t)(m * 16 + l15) * pitch + (s0 + i) * 32 + lg * 8);
@@ -80,6 +98,9 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(SkinnyArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) dst[(size_t)(m * 16 + lg * 4 + r) * p.N + n0 + l15] = acc[m][r];
 }
+
+template <int MT>
+__global__ __launch_bounds__(256) void gemm_skinny_kernel(SkinnyArgs p) { gemm_skinny_body<MT, SkinnyWBf16>(p); }
 
 struct SkinnyReduceArgs {
     const float* part;      // [KS][Mp][N]

@@ -31,6 +31,7 @@ static constexpr bool kLab = false;
 #include "k_sample.h"
 #include "k_skinny.h"
 #include "k_skinny_fp8.h"
+#include "skinny_plan.h"
 #include "k_mxfp4.h"
 #include "k_stc.h"
 #include "k_vit.h"
@@ -886,89 +887,65 @@ extern "C" int32_t vl2_row_stats(const void* x, float* stats, int32_t rows, int3
 }
 
 // ------------------------------------------------------------------------------------------------ skinny-M GEMM (batched decode)
-template <int MT>
-static void launch_skinny(const SkinnyArgs& a, int ks, size_t lds, hipStream_t s) {
-    lds_attr<gemm_skinny_kernel<MT>>(65536);
-    hipLaunchKernelGGL((gemm_skinny_kernel<MT>), dim3(a.N / 64, ks), dim3(256), lds, s, a);
+// ONE host routine behind the three weight formats' entries (16-bit, fp8 k_skinny_fp8.h, MXFP4 k_mxfp4.h): the common checks, the plan
+// (skinny_plan.h), the launch of the format's kernel (K1 / K2 / K4 = its MT = 1 / 2 / 4 instances) and the ordered reduce.  The entry checks
+// its own format's operands first and hands in `a` with the operands, shape and strides set, whether its layout rule holds (`layout_ok`,
+// reported as `rule` in its place in the order of checks), `row_scale` = the fp32 row scales the reduce applies (fp8) or null, and `shrink` =
+// the K split may shrink to fit the workspace (the 16-bit entry alone: the quantised entries pick the split from N and K only, so a row's bits
+// do not depend on M, and at the decode shapes and the default workspace it is the 16-bit kernel's split -- the output is
+// vl2_gemm_skinny_bf16's on the dequantised weights).  Every check precedes every launch.
+template <auto K1, auto K2, auto K4, class Args>
+static int32_t skinny_rows(const char* who, Args a, bool layout_ok, const char* rule, const float* row_scale, bool shrink, void* C, const float* bias,
+                           const void* res, int32_t ldc, int32_t ldres, int32_t flags, void* ws, int64_t ws_bytes, void* stream) {
+    const int M = a.M, N = a.N, K = a.K;
+    if (!a.A || !C || M <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "%s: null pointer or empty shape", who);
+    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
+    if (M > 64) return fail(VL2_E_SHAPE, "%s: M=%d rows, need M<=64 (split larger batches)", who, M);
+    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "%s: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", who, N);
+    if (K % 32) return fail(VL2_E_SHAPE, "%s: need K%%32==0 (K=%d)", who, K);
+    if (!layout_ok) return fail(VL2_E_SHAPE, "%s: need %s", who, rule);
+    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "%s: SWIGLU excludes bias / f32 output", who);
+    if (!ws || !ALIGNED16(ws) || ws_bytes <= 0) return fail(VL2_E_BADARG, "%s: needs a 16-byte aligned workspace (fp32 partial sums)", who);
+    SkinnyPlan pl;
+    const int rc = skinny_plan(M, N, K, ws_bytes, shrink, pl);
+    if (rc == SKINNY_PLAN_WS_SMALL) return fail(VL2_E_BADARG, "%s: workspace too small (%lld bytes, need %lld)", who, (long long)ws_bytes, (long long)pl.ws_need);
+    if (rc != SKINNY_PLAN_OK) return fail(VL2_E_SHAPE, "%s: no K chunking for K=%d", who, K);
+    a.part = (float*)ws;
+    a.kslice = pl.kslice;
+    a.kchunk = pl.kchunk;
+    hipStream_t s = ST(stream);
+    const dim3 gk(N / 64, pl.ks), b(256);
+    if (pl.mt == 1) { lds_attr<K1>(65536); hipLaunchKernelGGL(K1, gk, b, pl.lds, s, a); }
+    else if (pl.mt == 2) { lds_attr<K2>(65536); hipLaunchKernelGGL(K2, gk, b, pl.lds, s, a); }
+    else { lds_attr<K4>(65536); hipLaunchKernelGGL(K4, gk, b, pl.lds, s, a); }
+    SkinnyReduceArgs r{(const float*)ws, C, bias, (const bf16_t*)res, M, pl.Mp, N, pl.ks, ldc, ldres, row_scale};
+    const int ncol = sw ? N / 2 : N;
+    const dim3 g((M * (ncol / 4) + 255) / 256);
+#define VL2_SKR(SW, F32) do { if (row_scale) hipLaunchKernelGGL((skinny_reduce_kernel<SW, F32, true>), g, b, 0, s, r); \
+                              else hipLaunchKernelGGL((skinny_reduce_kernel<SW, F32, false>), g, b, 0, s, r); } while (0)
+    if (sw) VL2_SKR(true, false); else if (f32) VL2_SKR(false, true); else VL2_SKR(false, false);
+#undef VL2_SKR
+    return launched(who);
 }
+#define VL2_SKINNY_ROWS(KERN, ARGS) skinny_rows<KERN<1>, KERN<2>, KERN<4>, ARGS>
 extern "C" int32_t vl2_gemm_skinny_bf16(const void* A, const void* W, void* C, const float* bias, const void* res, int32_t M,
                                         int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc, int32_t ldres, int32_t flags,
                                         void* ws, int64_t ws_bytes, void* stream) {
-    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_bf16: null pointer or empty shape");
-    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
-    if (M > 64 || N % 64 || (sw && N % 128) || K % 32 || lda % 8 || ldw % 8 || ldc % 4 || (res && ldres % 4))
-        return fail(VL2_E_SHAPE, "vl2_gemm_skinny_bf16: need M<=64, N%%64==0, K%%32==0 (M=%d N=%d K=%d)", M, N, K);
-    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemm_skinny_bf16: SWIGLU excludes bias / f32 output");
-    if (!ws || !ALIGNED16(ws) || ws_bytes <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_bf16: needs a 16-byte aligned workspace (fp32 partial sums)");
-    const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4, Mp = 16 * mt;
-    const int steps = K / 32;
-    // K split: enough (column group, K slice) waves to keep ~4096 in flight, a divisor of the 32-deep steps, partials within
-    // the workspace
-    int ks = (4096 + N / 16 - 1) / (N / 16);
-    ks = ks < 1 ? 1 : ks > 32 ? 32 : ks;
-    while (ks > 1 && (steps % ks || (int64_t)ks * Mp * N * 4 > ws_bytes)) --ks;
-    if ((int64_t)ks * Mp * N * 4 > ws_bytes) return fail(VL2_E_BADARG, "vl2_gemm_skinny_bf16: workspace too small (%lld bytes)", (long long)ws_bytes);
-    const int kslice = K / ks;
-    int kchunk = kslice;                                      // largest 32-multiple divisor of the slice whose x chunk fits 64 KiB
-    while (kchunk > 32 && (kslice % kchunk || kchunk % 32 || (size_t)Mp * (kchunk + 8) * 2 > 65536)) kchunk -= 32;
-    if (kslice % kchunk || (size_t)Mp * (kchunk + 8) * 2 > 65536) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_bf16: no K chunking for K=%d", K);
-    SkinnyArgs a{(const bf16_t*)A, (const bf16_t*)W, (float*)ws, M, N, K, lda, ldw, kslice, kchunk};
-    const size_t lds = (size_t)Mp * (kchunk + 8) * 2;
-    hipStream_t s = ST(stream);
-    if (mt == 1) launch_skinny<1>(a, ks, lds, s); else if (mt == 2) launch_skinny<2>(a, ks, lds, s); else launch_skinny<4>(a, ks, lds, s);
-    SkinnyReduceArgs r{(const float*)ws, C, bias, (const bf16_t*)res, M, Mp, N, ks, ldc, ldres};
-    const int ncol = sw ? N / 2 : N;
-    const dim3 g((M * (ncol / 4) + 255) / 256), b(256);
-    if (sw) hipLaunchKernelGGL((skinny_reduce_kernel<true, false>), g, b, 0, s, r);
-    else if (f32) hipLaunchKernelGGL((skinny_reduce_kernel<false, true>), g, b, 0, s, r);
-    else hipLaunchKernelGGL((skinny_reduce_kernel<false, false>), g, b, 0, s, r);
-    return launched("vl2_gemm_skinny_bf16");
-}
-
-// fp8 weights (W8A16, k_skinny_fp8.h): the 16-bit launcher's grid, K chunking and reduce, the row scales applied in the reduce.  The K split
-// is chosen from N and K only -- never shrunk to fit the workspace, which is checked instead -- so a row's bits do not depend on M, and at the
-// decode shapes and the default workspace it is the 16-bit kernel's split (the output is vl2_gemm_skinny_bf16's on the dequantised weights).
-template <int MT>
-static void launch_skinny_fp8(const Skinny8Args& a, int ks, size_t lds, hipStream_t s) {
-    lds_attr<gemm_skinny_fp8_kernel<MT>>(65536);
-    hipLaunchKernelGGL((gemm_skinny_fp8_kernel<MT>), dim3(a.N / 64, ks), dim3(256), lds, s, a);
+    if (!W) return fail(VL2_E_BADARG, "vl2_gemm_skinny_bf16: null pointer or empty shape");
+    const bool ok = !(lda % 8 || ldw % 8 || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(W));
+    return VL2_SKINNY_ROWS(gemm_skinny_kernel, SkinnyArgs)("vl2_gemm_skinny_bf16", SkinnyArgs{(const bf16_t*)A, (const bf16_t*)W, nullptr, M, N, K, lda, ldw, 0, 0},
+                                                           ok, "16-byte aligned rows, lda%8==0, ldw%8==0, ldc%4==0, ldres%4==0", nullptr, true, C, bias, res,
+                                                           ldc, ldres, flags, ws, ws_bytes, stream);
 }
 extern "C" int32_t vl2_gemm_skinny_fp8(const void* A, const void* q, const float* scale, void* C, const float* bias, const void* res, int32_t M,
                                        int32_t N, int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws,
                                        int64_t ws_bytes, void* stream) {
     if (!q) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: null q (the e4m3fn weights)");
     if (!scale) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: null scale (the weights' row scales)");
-    if (!A || !C || M <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: null pointer or empty shape");
-    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
-    if (M > 64) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: M=%d rows, need M<=64 (split larger batches)", M);
-    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
-    if (K % 32) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: need K%%32==0 (K=%d)", K);
-    if (lda % 8 || lda < K || ldq % 16 || ldq < K || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(q))
-        return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: need 16-byte aligned rows, lda%%8==0, ldq%%16==0, ldc%%4==0, ldres%%4==0");
-    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemm_skinny_fp8: SWIGLU excludes bias / f32 output");
-    if (!ws || !ALIGNED16(ws) || ws_bytes <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: needs a 16-byte aligned workspace (fp32 partial sums)");
-    const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4, Mp = 16 * mt;
-    const int steps = K / 32;
-    int ks = (4096 + N / 16 - 1) / (N / 16);
-    ks = ks < 1 ? 1 : ks > 32 ? 32 : ks;
-    while (ks > 1 && steps % ks) --ks;
-    if ((int64_t)ks * Mp * N * 4 > ws_bytes)
-        return fail(VL2_E_BADARG, "vl2_gemm_skinny_fp8: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)ks * Mp * N * 4);
-    const int kslice = K / ks;
-    int kchunk = kslice;
-    while (kchunk > 32 && (kslice % kchunk || kchunk % 32 || (size_t)Mp * (kchunk + 8) * 2 > 65536)) kchunk -= 32;
-    if (kslice % kchunk || (size_t)Mp * (kchunk + 8) * 2 > 65536) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_fp8: no K chunking for K=%d", K);
-    Skinny8Args a{(const bf16_t*)A, (const uint8_t*)q, (float*)ws, M, N, K, lda, ldq, kslice, kchunk};
-    const size_t lds = (size_t)Mp * (kchunk + 8) * 2;
-    hipStream_t s = ST(stream);
-    if (mt == 1) launch_skinny_fp8<1>(a, ks, lds, s); else if (mt == 2) launch_skinny_fp8<2>(a, ks, lds, s); else launch_skinny_fp8<4>(a, ks, lds, s);
-    SkinnyReduceArgs r{(const float*)ws, C, bias, (const bf16_t*)res, M, Mp, N, ks, ldc, ldres, scale};
-    const int ncol = sw ? N / 2 : N;
-    const dim3 g((M * (ncol / 4) + 255) / 256), b(256);
-    if (sw) hipLaunchKernelGGL((skinny_reduce_kernel<true, false, true>), g, b, 0, s, r);
-    else if (f32) hipLaunchKernelGGL((skinny_reduce_kernel<false, true, true>), g, b, 0, s, r);
-    else hipLaunchKernelGGL((skinny_reduce_kernel<false, false, true>), g, b, 0, s, r);
-    return launched("vl2_gemm_skinny_fp8");
+    const bool ok = !(lda % 8 || lda < K || ldq % 16 || ldq < K || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(q));
+    return VL2_SKINNY_ROWS(gemm_skinny_fp8_kernel, Skinny8Args)("vl2_gemm_skinny_fp8", Skinny8Args{(const bf16_t*)A, (const uint8_t*)q, nullptr, M, N, K, lda, ldq, 0, 0},
+                                                                ok, "16-byte aligned rows, lda%8==0, ldq%16==0, ldc%4==0, ldres%4==0", scale, false, C, bias,
+                                                                res, ldc, ldres, flags, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ norms
@@ -1294,23 +1271,6 @@ extern "C" int32_t vl2_quant_act_fp8(const void* x, int64_t ldx, void* q, int64_
                        norm == VL2_NORM_RMS ? 1 : 0, eps);
     return launched("vl2_quant_act_fp8");
 }
-extern "C" int32_t vl2_gemv_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
-                                int32_t N, int32_t K, int32_t ldq, float eps, int32_t flags, void* stream) {
-    if (!q || !scale || !x || !y || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_gemv_fp8: bad args");
-    if (K % 16 || ldq % 16 || ldq < K || K > 32704 || N % 2) return fail(VL2_E_SHAPE, "vl2_gemv_fp8: need N even, K%%16==0, ldq%%16==0, K<=32704 (x lives in LDS as 16-bit elements; K=%d)", K);
-    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
-    if (sw && (N % 64 || f32 || bias)) return fail(VL2_E_SHAPE, "vl2_gemv_fp8: SWIGLU needs N%%64==0, 16-bit output, no bias");
-    Gemv8Args a{(const uint8_t*)q, scale, (const bf16_t*)x, norm_w, (const bf16_t*)res, y, N, K, ldq, eps, bias, 0};
-    if (flags & VL2_GEMV_RMS_PLAIN) { a.norm_w = nullptr; a.rms_plain = 1; }
-    const size_t lds = (size_t)K * 2;
-    const dim3 b(256);
-    // rows of K <= 4096 are four 16-B vectors per lane: two pairs per wave and trip keep the 16-bit kernel's bytes in flight (k_fp8.h)
-#define VL2_G8(SW, F32, NP) hipLaunchKernelGGL((gemv_fp8_kernel<SW, F32, NP>), dim3((unsigned)((N / 2 + 4 * NP - 1) / (4 * NP))), b, lds, ST(stream), a)
-    if (K <= 4096) { if (sw) VL2_G8(true, false, 2); else if (f32) VL2_G8(false, true, 2); else VL2_G8(false, false, 2); }
-    else           { if (sw) VL2_G8(true, false, 1); else if (f32) VL2_G8(false, true, 1); else VL2_G8(false, false, 1); }
-#undef VL2_G8
-    return launched("vl2_gemv_fp8");
-}
 template <bool SW, bool F32>
 static void launch_gemv_mr(const GemvArgs& a, int mb, int n_out, hipStream_t s) {
     // two output rows per wave amortise staging the MB rows of x: measured at B = 4, 5.56 / 5.04 / 5.56 ms per step at 1 / 2 / 4
@@ -1348,54 +1308,63 @@ extern "C" int32_t vl2_gemv_batched_bf16(const void* W, const void* x, const flo
     }
     return launched("vl2_gemv_batched_bf16");
 }
-// fp8 weights: rows of K <= 4096 two pairs per wave (NP = 2) as vl2_gemv_fp8; MB = 1 IS gemv_fp8_kernel, MB = 2..4 gemv_mr_fp8_kernel (k_fp8.h)
+// fp8 weights: rows of K <= 4096 are four 16-B vectors per lane: two pairs per wave and trip (NP = 2) keep the 16-bit kernel's bytes in flight
+// (k_fp8.h); MB = 1 is gemv_fp8_kernel, MB = 2..4 gemv_mr_fp8_kernel -- one body
 template <bool SW, bool F32>
-static void launch_gemv_fp8_rows(const Gemv8MrArgs& a, int mb, hipStream_t s) {
-    const int N = a.g.N, K = a.g.K;
-    const size_t lds = (size_t)mb * K * 2;
+static void launch_gemv_fp8_rows(const Gemv8Args& a, int mb, hipStream_t s) {
+    const size_t lds = (size_t)mb * a.K * 2;
     const dim3 b(256);
-    if (K <= 4096) {
-        const dim3 g((unsigned)((N / 2 + 7) / 8));
-        if (mb == 1) hipLaunchKernelGGL((gemv_fp8_kernel<SW, F32, 2>), g, b, lds, s, a.g);
-        else if (mb == 2) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 2, 2>), g, b, lds, s, a);
-        else if (mb == 3) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 2, 3>), g, b, lds, s, a);
-        else hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 2, 4>), g, b, lds, s, a);
-    } else {
-        const dim3 g((unsigned)((N / 2 + 3) / 4));
-        if (mb == 1) hipLaunchKernelGGL((gemv_fp8_kernel<SW, F32, 1>), g, b, lds, s, a.g);
-        else if (mb == 2) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 1, 2>), g, b, lds, s, a);
-        else if (mb == 3) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 1, 3>), g, b, lds, s, a);
-        else hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, 1, 4>), g, b, lds, s, a);
-    }
+#define VL2_G8(NP)                                                                                            \
+    do {                                                                                                      \
+        const dim3 g((unsigned)((a.N / 2 + 4 * NP - 1) / (4 * NP)));                                          \
+        if (mb == 1) hipLaunchKernelGGL((gemv_fp8_kernel<SW, F32, NP>), g, b, lds, s, a);                     \
+        else if (mb == 2) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, NP, 2>), g, b, lds, s, a);          \
+        else if (mb == 3) hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, NP, 3>), g, b, lds, s, a);          \
+        else hipLaunchKernelGGL((gemv_mr_fp8_kernel<SW, F32, NP, 4>), g, b, lds, s, a);                       \
+    } while (0)
+    if (a.K <= 4096) VL2_G8(2); else VL2_G8(1);
+#undef VL2_G8
 }
-extern "C" int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias,
-                                        void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps,
-                                        int32_t flags, void* stream) {
-    if (!q) return fail(VL2_E_BADARG, "vl2_gemv_batched_fp8: null q (the e4m3fn weights)");
-    if (!scale) return fail(VL2_E_BADARG, "vl2_gemv_batched_fp8: null scale (the weights' row scales)");
-    if (!x || !y || N <= 0 || K <= 0 || MB <= 0) return fail(VL2_E_BADARG, "vl2_gemv_batched_fp8: null pointer or empty shape");
-    if (K % 16 || K > 32704) return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: need K%%16==0, K<=32704 (x lives in LDS as 16-bit elements; K=%d)", K);
-    if (N % 2) return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: need N even (N=%d)", N);
+// ONE host routine behind vl2_gemv_fp8 (MB = 1, the rows' strides their widths) and vl2_gemv_batched_fp8.  `mix` = the code of "SWIGLU with
+// bias / f32 output", which the two entries have always reported differently.  Every check precedes every launch.
+static int32_t gemv_fp8_rows(const char* who, int32_t mix, const void* q, const float* scale, const void* x, const float* norm_w, const void* res,
+                             const float* bias, void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres,
+                             float eps, int32_t flags, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "%s: null q (the e4m3fn weights)", who);
+    if (!scale) return fail(VL2_E_BADARG, "%s: null scale (the weights' row scales)", who);
+    if (!x || !y || N <= 0 || K <= 0 || MB <= 0) return fail(VL2_E_BADARG, "%s: null pointer or empty shape", who);
+    if (K % 16 || K > 32704) return fail(VL2_E_SHAPE, "%s: need K%%16==0, K<=32704 (x lives in LDS as 16-bit elements; K=%d)", who, K);
+    if (N % 2) return fail(VL2_E_SHAPE, "%s: need N even (N=%d)", who, N);
     const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
     const int n_out = sw ? N / 2 : N;
     if (ldq % 16 || ldq < K || ldx % 8 || ldx < K || ldy < n_out || (res && (ldres < n_out)) || !ALIGNED16(q) || !ALIGNED16(x))
-        return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: need 16-byte aligned rows, ldq%%16==0, ldq>=K, ldx%%8==0, ldx>=K, ldy / ldres >= the output width");
-    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemv_batched_fp8: SWIGLU excludes bias / f32 output");
-    if (sw && N % 64) return fail(VL2_E_SHAPE, "vl2_gemv_batched_fp8: SWIGLU needs N%%64==0 (N=%d)", N);
+        return fail(VL2_E_SHAPE, "%s: need 16-byte aligned rows, ldq%%16==0, ldq>=K, ldx%%8==0, ldx>=K, ldy / ldres >= the output width", who);
+    if (sw && (bias || f32)) return fail(mix, "%s: SWIGLU excludes bias / f32 output", who);
+    if (sw && N % 64) return fail(VL2_E_SHAPE, "%s: SWIGLU needs N%%64==0 (N=%d)", who, N);
     const int esz = f32 ? 4 : 2;
     const int cap = 65536 / (K * 2) < 4 ? 65536 / (K * 2) : 4;        // x rows that fit the 64 KiB of LDS, at most 4 per pass
     const bool plain = flags & VL2_GEMV_RMS_PLAIN;
     for (int b0 = 0; b0 < MB;) {
         const int mb = MB - b0 < cap ? MB - b0 : cap;
-        Gemv8MrArgs a{{(const uint8_t*)q, scale, (const bf16_t*)x + (size_t)b0 * ldx, plain ? nullptr : norm_w,
-                       res ? (const bf16_t*)res + (size_t)b0 * ldres : nullptr, (char*)y + (size_t)b0 * ldy * esz, N, K, ldq, eps, bias, plain ? 1 : 0},
-                      ldx, ldy, ldres};
+        Gemv8Args a{(const uint8_t*)q, scale, (const bf16_t*)x + (size_t)b0 * ldx, plain ? nullptr : norm_w,
+                    res ? (const bf16_t*)res + (size_t)b0 * ldres : nullptr, (char*)y + (size_t)b0 * ldy * esz, N, K, ldq, eps, bias, plain ? 1 : 0,
+                    ldx, ldy, ldres};
         if (sw) launch_gemv_fp8_rows<true, false>(a, mb, ST(stream));
         else if (f32) launch_gemv_fp8_rows<false, true>(a, mb, ST(stream));
         else launch_gemv_fp8_rows<false, false>(a, mb, ST(stream));
         b0 += mb;
     }
-    return launched("vl2_gemv_batched_fp8");
+    return launched(who);
+}
+extern "C" int32_t vl2_gemv_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias, void* y,
+                                int32_t N, int32_t K, int32_t ldq, float eps, int32_t flags, void* stream) {
+    const int n_out = (flags & VL2_GEMM_SWIGLU) ? N / 2 : N;
+    return gemv_fp8_rows("vl2_gemv_fp8", VL2_E_SHAPE, q, scale, x, norm_w, res, bias, y, 1, N, K, ldq, K, n_out, n_out, eps, flags, stream);
+}
+extern "C" int32_t vl2_gemv_batched_fp8(const void* q, const float* scale, const void* x, const float* norm_w, const void* res, const float* bias,
+                                        void* y, int32_t MB, int32_t N, int32_t K, int32_t ldq, int32_t ldx, int32_t ldy, int32_t ldres, float eps,
+                                        int32_t flags, void* stream) {
+    return gemv_fp8_rows("vl2_gemv_batched_fp8", VL2_E_UNSUPP, q, scale, x, norm_w, res, bias, y, MB, N, K, ldq, ldx, ldy, ldres, eps, flags, stream);
 }
 // ---- MXFP4 weights (k_mxfp4.h): q [N, ldq] bytes of two E2M1 codes, s [N, lds] E8M0 bytes (one per 32 k).  Every check precedes every launch.
 extern "C" int32_t vl2_pack_quant_mxfp4(const void* w, int64_t N, int64_t K, int64_t ldw, void* q, void* s, int64_t lds, void* stream) {
@@ -1467,49 +1436,17 @@ extern "C" int32_t vl2_gemv_batched_mxfp4(const void* q, const void* scale, int3
                                           int32_t ldres, float eps, int32_t flags, void* stream) {
     return gemv_mxfp4_rows("vl2_gemv_batched_mxfp4", q, scale, lds, x, norm_w, res, bias, y, MB, N, K, ldq, ldx, ldy, ldres, eps, flags, stream);
 }
-// skinny-M on the MXFP4 weights: vl2_gemm_skinny_fp8's grid, K split (from N and K only, never shrunk to fit the workspace), chunking and ordered
-// reduce; the block scales ride in the conversion, so the reduce is the unscaled one
-template <int MT>
-static void launch_skinny_mxfp4(const Skinny4Args& a, int ks, size_t lds, hipStream_t s) {
-    lds_attr<gemm_skinny_mxfp4_kernel<MT>>(65536);
-    hipLaunchKernelGGL((gemm_skinny_mxfp4_kernel<MT>), dim3(a.N / 64, ks), dim3(256), lds, s, a);
-}
+// skinny-M on the MXFP4 weights (skinny_rows above): the block scales ride in the conversion, so the reduce is the unscaled one
 extern "C" int32_t vl2_gemm_skinny_mxfp4(const void* A, const void* q, const void* scale, int32_t lds_, void* C, const float* bias, const void* res,
                                          int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldq, int32_t ldc, int32_t ldres, int32_t flags, void* ws,
                                          int64_t ws_bytes, void* stream) {
     if (!q) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: null q (the E2M1 codes)");
     if (!scale) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: null scale (the E8M0 block scales)");
-    if (!A || !C || M <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: null pointer or empty shape");
-    const bool sw = flags & VL2_GEMM_SWIGLU, f32 = flags & VL2_GEMM_OUT_F32;
-    if (M > 64) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: M=%d rows, need M<=64 (split larger batches)", M);
-    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
-    if (K % 32) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: need K%%32==0 (K=%d)", K);
-    if (lda % 8 || lda < K || ldq % 16 || ldq < K / 2 || lds_ < K / 32 || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(q))
-        return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: need 16-byte aligned rows, lda%%8==0, ldq%%16==0, ldq>=K/2, lds>=K/32, ldc%%4==0, ldres%%4==0");
-    if (sw && (bias || f32)) return fail(VL2_E_UNSUPP, "vl2_gemm_skinny_mxfp4: SWIGLU excludes bias / f32 output");
-    if (!ws || !ALIGNED16(ws) || ws_bytes <= 0) return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: needs a 16-byte aligned workspace (fp32 partial sums)");
-    const int mt = M <= 16 ? 1 : M <= 32 ? 2 : 4, Mp = 16 * mt;
-    const int steps = K / 32;
-    int ks = (4096 + N / 16 - 1) / (N / 16);
-    ks = ks < 1 ? 1 : ks > 32 ? 32 : ks;
-    while (ks > 1 && steps % ks) --ks;
-    if ((int64_t)ks * Mp * N * 4 > ws_bytes)
-        return fail(VL2_E_BADARG, "vl2_gemm_skinny_mxfp4: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)ks * Mp * N * 4);
-    const int kslice = K / ks;
-    int kchunk = kslice;
-    while (kchunk > 32 && (kslice % kchunk || kchunk % 32 || (size_t)Mp * (kchunk + 8) * 2 > 65536)) kchunk -= 32;
-    if (kslice % kchunk || (size_t)Mp * (kchunk + 8) * 2 > 65536) return fail(VL2_E_SHAPE, "vl2_gemm_skinny_mxfp4: no K chunking for K=%d", K);
-    Skinny4Args a{(const bf16_t*)A, (const uint8_t*)q, (const uint8_t*)scale, (float*)ws, M, N, K, lda, ldq, lds_, kslice, kchunk};
-    const size_t lds = (size_t)Mp * (kchunk + 8) * 2;
-    hipStream_t s = ST(stream);
-    if (mt == 1) launch_skinny_mxfp4<1>(a, ks, lds, s); else if (mt == 2) launch_skinny_mxfp4<2>(a, ks, lds, s); else launch_skinny_mxfp4<4>(a, ks, lds, s);
-    SkinnyReduceArgs r{(const float*)ws, C, bias, (const bf16_t*)res, M, Mp, N, ks, ldc, ldres};
-    const int ncol = sw ? N / 2 : N;
-    const dim3 g((M * (ncol / 4) + 255) / 256), b(256);
-    if (sw) hipLaunchKernelGGL((skinny_reduce_kernel<true, false>), g, b, 0, s, r);
-    else if (f32) hipLaunchKernelGGL((skinny_reduce_kernel<false, true>), g, b, 0, s, r);
-    else hipLaunchKernelGGL((skinny_reduce_kernel<false, false>), g, b, 0, s, r);
-    return launched("vl2_gemm_skinny_mxfp4");
+    const bool ok = !(lda % 8 || lda < K || ldq % 16 || ldq < K / 2 || lds_ < K / 32 || ldc % 4 || (res && ldres % 4) || !ALIGNED16(A) || !ALIGNED16(q));
+    return VL2_SKINNY_ROWS(gemm_skinny_mxfp4_kernel, Skinny4Args)(
+        "vl2_gemm_skinny_mxfp4", Skinny4Args{(const bf16_t*)A, (const uint8_t*)q, (const uint8_t*)scale, nullptr, M, N, K, lda, ldq, lds_, 0, 0}, ok,
+        "16-byte aligned rows, lda%8==0, ldq%16==0, ldq>=K/2, lds>=K/32, ldc%4==0, ldres%4==0", nullptr, false, C, bias, res, ldc, ldres, flags, ws, ws_bytes,
+        stream);
 }
 extern "C" int32_t vl2_attn_decode(const void* qkv, void* kcache, void* vcache, const float* cos_t, const float* sin_t,
                                    float* partial, void* out, int32_t nh, int32_t nkv, int32_t smax, int32_t pos,

@@ -376,14 +376,19 @@ def gemm_fp8(a8, row_tab, w8, col_scale, bias=None, res=None, act=ACT_NONE, swig
     return out
 
 
+def _out_flags(rows, N, swiglu, out_f32, out, device, rms_plain=False):
+    """The output tensor ([rows, n_out]; [n_out] for rows = None) and the flag word of a decode projection on quantised weights."""
+    n_out = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((n_out,) if rows is None else (rows, n_out), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=device)
+    return out, (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+
+
 def gemv_fp8(q, scale, x, norm_w=None, eps=1e-5, res=None, swiglu=False, out_f32=False, out=None, bias=None, rms_plain=False):
     """y = scale * (q @ x) (+ bias) (+ res) for one token on fp8 weights (include/vl2hip.h vl2_gemv_fp8; W8A16)."""
     _chk(q, torch.uint8, "q"); _chk(scale, torch.float32, "scale"); _chk(x, _lib.elem_dtype(), "x"); _chk(bias, torch.float32, "bias")
     N, K = q.shape
-    n_out = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((n_out,), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
-    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    out, flags = _out_flags(None, N, swiglu, out_f32, out, q.device, rms_plain)
     _lib.call("vl2_gemv_fp8", _p(q), _p(scale), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), N, K, q.stride(0), float(eps), flags, _stream())
     return out
 
@@ -426,10 +431,7 @@ def gemm_skinny_fp8(a, q, scale, bias=None, res=None, swiglu=False, out_f32=Fals
     _chk(res, _lib.elem_dtype(), "res")
     M, K = a.shape
     N = q.shape[0]
-    ncol = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((M, ncol), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=a.device)
-    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0)
+    out, flags = _out_flags(M, N, swiglu, out_f32, out, a.device)
     ws = attach_workspace(a.device)
     for m0 in range(0, M, 64):
         m1 = min(M, m0 + 64)
@@ -445,10 +447,7 @@ def gemv_batched_fp8(q, scale, x, norm_w=None, eps=1e-5, res=None, swiglu=False,
     _chk(res, _lib.elem_dtype(), "res")
     N, K = q.shape
     MB = x.shape[0]
-    n_out = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((MB, n_out), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
-    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    out, flags = _out_flags(MB, N, swiglu, out_f32, out, q.device, rms_plain)
     _lib.call("vl2_gemv_batched_fp8", _p(q), _p(scale), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), MB, N, K, q.stride(0), x.stride(0),
               out.stride(0), 0 if res is None else res.stride(0), float(eps), flags, _stream())
     return out
@@ -477,10 +476,7 @@ def _mxfp4_args(q, s, x, bias, res):
 def gemv_mxfp4(q, s, x, norm_w=None, eps=1e-5, res=None, swiglu=False, out_f32=False, out=None, bias=None, rms_plain=False):
     """y = W~ x (+ bias) (+ res) for one token on MXFP4 weights (include/vl2hip.h vl2_gemv_mxfp4; W4A16): q, s from `quant_mxfp4`."""
     N, K = _mxfp4_args(q, s, x, bias, res)
-    n_out = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((n_out,), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
-    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    out, flags = _out_flags(None, N, swiglu, out_f32, out, q.device, rms_plain)
     _lib.call("vl2_gemv_mxfp4", _p(q), _p(s), s.stride(0), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), N, K, q.stride(0), float(eps), flags,
               _stream())
     return out
@@ -491,10 +487,7 @@ def gemv_batched_mxfp4(q, s, x, norm_w=None, eps=1e-5, res=None, swiglu=False, o
     vl2_gemv_batched_mxfp4): every row bit for bit the single-row call.  res / out are [MB, n_out]."""
     N, K = _mxfp4_args(q, s, x, bias, res)
     MB = x.shape[0]
-    n_out = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((MB, n_out), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=q.device)
-    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0) | (GEMV_RMS_PLAIN if rms_plain else 0)
+    out, flags = _out_flags(MB, N, swiglu, out_f32, out, q.device, rms_plain)
     _lib.call("vl2_gemv_batched_mxfp4", _p(q), _p(s), s.stride(0), _p(x), _p(norm_w), _p(res), _p(bias), _p(out), MB, N, K, q.stride(0),
               x.stride(0), out.stride(0), 0 if res is None else res.stride(0), float(eps), flags, _stream())
     return out
@@ -506,10 +499,7 @@ def gemm_skinny_mxfp4(a, q, s, bias=None, res=None, swiglu=False, out_f32=False,
     lands in).  Needs `attach_workspace`."""
     N, K = _mxfp4_args(q, s, a, bias, res)
     M = a.shape[0]
-    ncol = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((M, ncol), dtype=torch.float32 if out_f32 else _lib.elem_dtype(), device=a.device)
-    flags = (GEMM_SWIGLU if swiglu else 0) | (GEMM_OUT_F32 if out_f32 else 0)
+    out, flags = _out_flags(M, N, swiglu, out_f32, out, a.device)
     ws = attach_workspace(a.device)
     for m0 in range(0, M, 64):
         m1 = min(M, m0 + 64)
