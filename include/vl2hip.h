@@ -341,6 +341,26 @@ int32_t vl2_attn_decode(const void* qkv, void* kcache, void* vcache, const float
 int32_t vl2_attn_decode_batched(const void* qkv, void* kcache, void* vcache, const float* cos_t, const float* sin_t, float* partial,
                                 void* out, int32_t B, int64_t qkv_bs, int64_t cache_bs, int64_t out_bs, int32_t nh, int32_t nkv,
                                 int32_t smax, const int32_t* pos_dev, int32_t ctx_cap, float scale, void* stream);
+/* ---- fp8 KV cache for decode (csrc/k_kv8.h; additions of ABI 7).  Per layer: k8 / v8 = uint8 [nkv, smax, 128] OCP e4m3fn codes, ks / vs = fp32
+ * [nkv, smax]: ONE power-of-two scale 2^e per (kv head, position) row of 128 elements, K and V apart, e = the smallest integer with
+ * max|row| <= 448 * 2^e (the rule of vl2_pack_quant_fp8's weight rows; a zero row: scale 1).  Quantised is the 16-bit cache row as the 16-bit
+ * path stores it (K roped and rounded to the element type).  head_dim 128.  An OPTIONAL arithmetic, never a default.
+ * vl2_kv_quant: rows [p0, p1) of one sequence's 16-bit caches k16 / v16 [nkv, smax, 128] -> codes and scales at the same rows of k8 / v8 / ks / vs
+ *   (one launch for K and V; nothing outside those rows is written).
+ * vl2_attn_decode_kv8: vl2_attn_decode on the fp8 cache (same qkv, positions, partial workspace and out): ropes q, ropes k_new, rounds it to the
+ *   element type, quantises it and v_new into row pos (codes and scales), then the same split attention and combine.  bf16 build: bit for bit
+ *   vl2_attn_decode on the dequantised cache code * 2^e (exact in bf16) whenever the new row is on the fp8 grid -- otherwise the two differ by
+ *   that row's quantisation, which vl2_attn_decode does not apply; fp16 build: equal to rounding.
+ * vl2_attn_decode_kv8_batched: B sequences as vl2_attn_decode_batched; sequence b's codes at k8 / v8 + b*cache_bs (bytes), its scales at
+ *   ks / vs + b*scale_bs (floats).  pos_dev[b] >= smax: sequence b writes nothing. */
+int32_t vl2_kv_quant(const void* k16, const void* v16, void* k8, void* v8, float* ks, float* vs, int32_t nkv, int32_t smax, int32_t p0, int32_t p1,
+                     void* stream);
+int32_t vl2_attn_decode_kv8(const void* qkv, void* k8, void* v8, float* ks, float* vs, const float* cos_t, const float* sin_t, float* partial,
+                            void* out, int32_t nh, int32_t nkv, int32_t smax, int32_t pos, const int32_t* pos_dev, int32_t ctx_cap, float scale,
+                            void* stream);
+int32_t vl2_attn_decode_kv8_batched(const void* qkv, void* k8, void* v8, float* ks, float* vs, const float* cos_t, const float* sin_t, float* partial,
+                                    void* out, int32_t B, int64_t qkv_bs, int64_t cache_bs, int64_t scale_bs, int64_t out_bs, int32_t nh, int32_t nkv,
+                                    int32_t smax, const int32_t* pos_dev, int32_t ctx_cap, float scale, void* stream);
 /* Append attention (k_attn_append.h): n new query rows at positions P .. P+n-1 of ONE sequence against the P + n keys of its cache
  * (the rows P .. P+n-1 already written, e.g. by vl2_rope_kv with pos0 = P); key j is visible to row i iff j <= P + i.  q: roped rows
  * [n, q_rs] (q head h at column h*128), caches [nkv, smax, 128], out [n, o_rs] 16-bit.  head_dim 128 only.  Split-KV: fp32 partials of

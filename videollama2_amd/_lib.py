@@ -140,8 +140,14 @@ MXFP4_SIGNATURES = {
     "vl2_gemv_batched_mxfp4": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "vl2_gemm_skinny_mxfp4": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
 }
+# the fp8 KV cache of the decode step (include/vl2hip.h vl2_kv_quant / vl2_attn_decode_kv8[_batched], csrc/k_kv8.h): a table of its own for the same reason
+FP8KV_SIGNATURES = {
+    "vl2_kv_quant": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "vl2_attn_decode_kv8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _vp],
+    "vl2_attn_decode_kv8_batched": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _f32, _vp],
+}
 EXPORTS = ["vl2_version", "vl2_elem_name", "vl2_last_error_string", "vl2_workspace_bytes", "vl2_vit_workspace_bytes", "vl2_stc_workspace_bytes", "vl2_llm_workspace_bytes", "vl2_dwconv_mean_workspace_bytes", "vl2_attn_append_ws_bytes"] + list(SIGNATURES) + list(MOE_SIGNATURES) + list(APPEND_SIGNATURES) + \
-    list(SAMPLE_ROWS_SIGNATURES) + list(FP8_BATCH_SIGNATURES) + list(MXFP4_SIGNATURES)
+    list(SAMPLE_ROWS_SIGNATURES) + list(FP8_BATCH_SIGNATURES) + list(MXFP4_SIGNATURES) + list(FP8KV_SIGNATURES)
 
 _lib = None
 # ---- element type of the build in use: "bf16" (libvl2hip.so, the default: BASELINE.json configs[1]) or "fp16" (libvl2hip_f16.so = the same
@@ -242,7 +248,8 @@ def load():
     lib.vl2_attn_append_ws_bytes.restype = _i64
     lib.vl2_attn_append_ws_bytes.argtypes = [_i32, _i32, _i32]
     for name, args in list(SIGNATURES.items()) + list(MOE_SIGNATURES.items()) + list(APPEND_SIGNATURES.items()) + \
-            list(SAMPLE_ROWS_SIGNATURES.items()) + list(FP8_BATCH_SIGNATURES.items()) + list(MXFP4_SIGNATURES.items()):
+            list(SAMPLE_ROWS_SIGNATURES.items()) + list(FP8_BATCH_SIGNATURES.items()) + list(MXFP4_SIGNATURES.items()) + \
+            list(FP8KV_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = _i32
         fn.argtypes = args

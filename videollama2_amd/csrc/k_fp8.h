@@ -21,6 +21,31 @@ typedef float vl2_f32x2_t __attribute__((ext_vector_type(2)));
 #define VL2_CVT_PK_FP8_F32(a, b, old, hi) __builtin_amdgcn_cvt_pk_fp8_f32((a), (b), (old), (hi))
 #endif
 
+// ---- THE per-row arithmetic of every e4m3fn quantiser here (weight rows, activation rows, KV-cache rows in k_kv8.h): one copy, so they
+// agree to the bit.  Scale: 448 = 1.75 * 2^8: amax = 1.f * 2^x  ->  e = x - 8 (+1 if 1.f > 1.75), clamped to [-100, 100]; sc = 2^e and
+// inv = 2^-e are exact floats (a zero or denormal-only row: e = 0).
+__device__ __forceinline__ void fp8_row_scale(float amax, float& sc, float& inv) {
+    const unsigned ab = __builtin_bit_cast(unsigned, amax);
+    const int E = (int)((ab >> 23) & 0xffu);
+    int e = E == 0 ? 0 : (E - 127) - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
+    e = e < -100 ? -100 : (e > 100 ? 100 : e);
+    sc = __builtin_bit_cast(float, (unsigned)(127 + e) << 23);
+    inv = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
+}
+// two values -> two e4m3fn bytes (bits 15:0): RNE of v * inv (v_cvt_pk_fp8_f32)
+__device__ __forceinline__ unsigned fp8_quant2(float v0, float v1, float inv) {
+    return (unsigned)VL2_CVT_PK_FP8_F32(v0 * inv, v1 * inv, 0, false) & 0xffffu;
+}
+// eight consecutive values -> eight e4m3fn bytes
+__device__ __forceinline__ u32x2 fp8_quant8(const float* v, float inv) {
+    int lo = 0, hi = 0;
+    lo = VL2_CVT_PK_FP8_F32(v[0] * inv, v[1] * inv, lo, false);
+    lo = VL2_CVT_PK_FP8_F32(v[2] * inv, v[3] * inv, lo, true);
+    hi = VL2_CVT_PK_FP8_F32(v[4] * inv, v[5] * inv, hi, false);
+    hi = VL2_CVT_PK_FP8_F32(v[6] * inv, v[7] * inv, hi, true);
+    return u32x2{(unsigned)lo, (unsigned)hi};
+}
+
 // grid = N rows, block 256.  w [N, ldw] 16-bit elements, q [N, K] bytes (K % 16 == 0), scale [N] fp32.
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __restrict__ w, uint8_t* __restrict__ q, float* __restrict__ scale,
                                                              int K, long ldw) {
@@ -38,25 +63,14 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
     if (lane == 0) red[wave] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    // 448 = 1.75 * 2^8: amax = 1.f * 2^x  ->  e = x - 8 (+1 if 1.f > 1.75), clamped; scale = 2^e and 2^-e are exact floats
-    const unsigned ab = __builtin_bit_cast(unsigned, amax);
-    const int E = (int)((ab >> 23) & 0xffu);
-    int e = E == 0 ? 0 : (E - 127) - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    const float sc = __builtin_bit_cast(float, (unsigned)(127 + e) << 23), inv = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
+    float sc, inv;
+    fp8_row_scale(amax, sc, inv);
     if (tid == 0) scale[blockIdx.x] = sc;
     uint8_t* qrow = q + (size_t)blockIdx.x * K;
     for (int k = tid * 8; k < K; k += 2048) {
         float v[8];
         unpack8(*(const u32x4*)(row + k), v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] * inv;
-        int lo = 0, hi = 0;
-        lo = VL2_CVT_PK_FP8_F32(v[0], v[1], lo, false);
-        lo = VL2_CVT_PK_FP8_F32(v[2], v[3], lo, true);
-        hi = VL2_CVT_PK_FP8_F32(v[4], v[5], hi, false);
-        hi = VL2_CVT_PK_FP8_F32(v[6], v[7], hi, true);
-        *(u32x2*)(qrow + k) = u32x2{(unsigned)lo, (unsigned)hi};
+        *(u32x2*)(qrow + k) = fp8_quant8(v, inv);
     }
 }
 
@@ -84,11 +98,8 @@ __global__ __launch_bounds__(256) void quant_act_fp8_kernel(const bf16_t* __rest
     __syncthreads();
     amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     ss = (red[4] + red[5]) + (red[6] + red[7]);
-    const unsigned ab = __builtin_bit_cast(unsigned, amax);             // the scale exponent: quant_fp8_rows_kernel's bit arithmetic
-    const int E = (int)((ab >> 23) & 0xffu);
-    int e = E == 0 ? 0 : (E - 127) - 8 + ((ab & 0x7fffffu) > 0x600000u ? 1 : 0);
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
-    const float sc = __builtin_bit_cast(float, (unsigned)(127 + e) << 23), inv = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
+    float sc, inv;
+    fp8_row_scale(amax, sc, inv);
     if (tid == 0) {
         rowtab[2 * (size_t)blockIdx.x] = 0.f;
         rowtab[2 * (size_t)blockIdx.x + 1] = rms ? sc * rsqrtf(ss / (float)K + eps) : sc;
@@ -97,14 +108,7 @@ __global__ __launch_bounds__(256) void quant_act_fp8_kernel(const bf16_t* __rest
     for (int k = tid * 8; k < K; k += 2048) {
         float v[8];
         unpack8(*(const u32x4*)(row + k), v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] * inv;
-        int lo = 0, hi = 0;
-        lo = VL2_CVT_PK_FP8_F32(v[0], v[1], lo, false);
-        lo = VL2_CVT_PK_FP8_F32(v[2], v[3], lo, true);
-        hi = VL2_CVT_PK_FP8_F32(v[4], v[5], hi, false);
-        hi = VL2_CVT_PK_FP8_F32(v[6], v[7], hi, true);
-        *(u32x2*)(qrow + k) = u32x2{(unsigned)lo, (unsigned)hi};
+        *(u32x2*)(qrow + k) = fp8_quant8(v, inv);
     }
 }
 

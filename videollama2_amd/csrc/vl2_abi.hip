@@ -37,6 +37,7 @@ static constexpr bool kLab = false;
 #include "k_vit.h"
 #include "k_moe.h"
 #include "k_attn_append.h"
+#include "k_kv8.h"
 
 static thread_local char g_err[512] = "";
 static int32_t fail(int32_t code, const char* fmt, ...) {
@@ -1502,6 +1503,48 @@ extern "C" int32_t vl2_attn_decode_batched(const void* qkv, void* kcache, void* 
     hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(nh, B), dim3(128), 0, ST(stream), partial, (bf16_t*)out, nsplit, 0, pos_dev,
                        partial_bs, (long)out_bs);
     return launched("vl2_attn_decode_batched");
+}
+// ---- fp8 KV cache (k_kv8.h): the quantiser of cache rows and the decode attention on the quantised cache
+extern "C" int32_t vl2_kv_quant(const void* k16, const void* v16, void* k8, void* v8, float* ks, float* vs, int32_t nkv, int32_t smax, int32_t p0,
+                                int32_t p1, void* stream) {
+    if (!k16 || !v16 || !k8 || !v8 || !ks || !vs || nkv <= 0 || smax <= 0) return fail(VL2_E_BADARG, "vl2_kv_quant: bad args");
+    if (p0 < 0 || p1 <= p0 || p1 > smax) return fail(VL2_E_SHAPE, "vl2_kv_quant: rows [%d, %d) outside the cache (%d)", p0, p1, smax);
+    if (!ALIGNED16(k16) || !ALIGNED16(v16) || !ALIGNED16(k8) || !ALIGNED16(v8)) return fail(VL2_E_SHAPE, "vl2_kv_quant: need 16-byte aligned caches");
+    const long nrows = 2L * nkv * (p1 - p0);
+    hipLaunchKernelGGL(kv_quant_rows_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, ST(stream), (const bf16_t*)k16, (const bf16_t*)v16,
+                       (uint8_t*)k8, (uint8_t*)v8, ks, vs, nkv, smax, p0, p1);
+    return launched("vl2_kv_quant");
+}
+static int32_t attn_decode_kv8(const char* who, const void* qkv, void* k8, void* v8, float* ks, float* vs, const float* cos_t, const float* sin_t,
+                               float* partial, void* out, int B, long qkv_bs, long cache_bs, long scale_bs, long out_bs, int nh, int nkv, int smax,
+                               int pos, const int32_t* pos_dev, int cap, float scale, void* stream) {
+    if (!qkv || !k8 || !v8 || !ks || !vs || !cos_t || !sin_t || !partial || !out || nh <= 0 || nkv <= 0 || B <= 0)
+        return fail(VL2_E_BADARG, "%s: bad args", who);
+    const int group = nh / nkv;
+    if (group * nkv != nh) return fail(VL2_E_SHAPE, "%s: need nh = nkv*group", who);
+    if (cap <= 0 || cap > smax || (!pos_dev && pos < 0)) return fail(VL2_E_SHAPE, "%s: position %d outside the cache (%d)", who, cap - 1, smax);
+    if (!ALIGNED16(k8) || !ALIGNED16(v8) || cache_bs % 16) return fail(VL2_E_SHAPE, "%s: need 16-byte aligned caches", who);
+    const int nsplit = (cap + 63) / 64;
+    const long partial_bs = (long)nh * nsplit * 130;
+    hipLaunchKernelGGL(attn_decode_kv8_kernel, dim3(nsplit, nkv * B, (group + 3) / 4), dim3(256), 0, ST(stream), (const bf16_t*)qkv, (uint8_t*)k8,
+                       (uint8_t*)v8, ks, vs, cos_t, sin_t, partial, nh, group, nkv, smax, pos, pos_dev, scale * 1.4426950408889634f, qkv_bs, cache_bs,
+                       scale_bs, partial_bs);
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(nh, B), dim3(128), 0, ST(stream), partial, (bf16_t*)out, nsplit, pos, pos_dev, partial_bs, out_bs);
+    return launched(who);
+}
+extern "C" int32_t vl2_attn_decode_kv8(const void* qkv, void* k8, void* v8, float* ks, float* vs, const float* cos_t, const float* sin_t, float* partial,
+                                       void* out, int32_t nh, int32_t nkv, int32_t smax, int32_t pos, const int32_t* pos_dev, int32_t ctx_cap,
+                                       float scale, void* stream) {
+    return attn_decode_kv8("vl2_attn_decode_kv8", qkv, k8, v8, ks, vs, cos_t, sin_t, partial, out, 1, 0L, 0L, 0L, 0L, nh, nkv, smax, pos, pos_dev,
+                           pos_dev ? ctx_cap : pos + 1, scale, stream);
+}
+extern "C" int32_t vl2_attn_decode_kv8_batched(const void* qkv, void* k8, void* v8, float* ks, float* vs, const float* cos_t, const float* sin_t,
+                                               float* partial, void* out, int32_t B, int64_t qkv_bs, int64_t cache_bs, int64_t scale_bs, int64_t out_bs,
+                                               int32_t nh, int32_t nkv, int32_t smax, const int32_t* pos_dev, int32_t ctx_cap, float scale,
+                                               void* stream) {
+    if (!pos_dev) return fail(VL2_E_BADARG, "vl2_attn_decode_kv8_batched: bad args (null pos_dev)");
+    return attn_decode_kv8("vl2_attn_decode_kv8_batched", qkv, k8, v8, ks, vs, cos_t, sin_t, partial, out, B, (long)qkv_bs, (long)cache_bs,
+                           (long)scale_bs, (long)out_bs, nh, nkv, smax, 0, pos_dev, ctx_cap, scale, stream);
 }
 // Split of the keys for vl2_attn_append: enough (kv head, row block, split) workgroups to fill the 256 CUs, at least two 64-key tiles per
 // split (a split's fp32 partials cost about what one tile's loads do), at most APPEND_MAX_SPLITS.

@@ -176,6 +176,7 @@ class HipMistralDecoder(nn.Module):
         # rank is the identity), so that the captured-RCCL decode graph can be exercised on hardware without a second GPU
         self.tp_always_reduce = False
         self.decode_fp8 = self.prefill_fp8 = self.decode_mxfp4 = False
+        self._fp8_kv, self.kv8 = False, None        # enable_fp8_kv: per layer (k8, v8, ks, vs), the single-sequence fp8 KV cache
 
     @property
     def decode_format(self):
@@ -218,6 +219,56 @@ class HipMistralDecoder(nn.Module):
         self._invalidate_graphs()                                 # a captured step holds the other projections
         self.cache_epoch += 1
         return self
+
+    FP8_KV_EXTEND_MSG = ("the fp8 KV cache is on: extend / generate(prefix_cache=True) are not built on it (the answer's rows exist only in "
+                         "fp8 and the append attention reads 16-bit rows): call enable_fp8_kv(False) first, or prefill the whole prompt")
+
+    @property
+    def fp8_kv(self):
+        """Whether the decode steps keep and read the KV cache in fp8 (enable_fp8_kv)."""
+        return self._fp8_kv
+
+    def _fp8_kv_refusals(self):
+        if self.tp > 1 or self.tp_group is not None or self.tp_local is not None or self.tp_always_reduce:
+            raise NotImplementedError("fp8 KV cache: single-rank decoders only (no tensor-parallel shard's cache is built in fp8): build the "
+                                      "decoder without a tensor-parallel group, or keep the 16-bit cache")
+        if self.hd != 128:
+            raise NotImplementedError(f"fp8 KV cache: head_dim 128 only (this decoder has {self.hd}): keep the 16-bit cache")
+
+    @torch.no_grad()
+    def enable_fp8_kv(self, on=True):
+        """OPTIONAL arithmetic: the decode steps keep the KV cache in fp8 (OCP e4m3fn codes with one power-of-two scale per (kv head,
+        position) row of 128 elements, K and V apart; csrc/k_kv8.h) -- half the attention's bytes per step and 0.52 x
+        the slots' memory.  Orthogonal to `decode_format`: 16-bit, fp8 and MXFP4 decode weights all run on it.  The 16-bit cache stays as
+        the prefill's staging cache: `prefill` is unchanged (same bits, its attention reads the 16-bit rows), its rows are then quantised
+        once, and `decode_step` / `capture_graph` / `generate` attend on the fp8 cache alone, the new token's rows quantised on their way in
+        (the step runs operator by operator: the stage call has no form for it).  The batched paths (`generate_batch`, ContinuousBatcher)
+        hold their slots in fp8 only and prefill through one 16-bit staging cache.  Switching drops every captured graph and the slot
+        buffers and resets the single-sequence state (pos = 0, a new cache_epoch); it is refused while a batcher holds requests in flight.
+        While it is on the decoder holds both single-sequence caches (+0.52 x the 16-bit one); switching it off frees the fp8 one.
+        `extend` / prefix reuse, tensor parallelism, Mixtral and head_dim != 128 raise NotImplementedError.  Not the reference's
+        arithmetic and never the default: with it off every path keeps its bits; tests/fp8kv_oracle.py defines the format."""
+        if on:
+            self._fp8_kv_refusals()
+        busy = getattr(self, "_bb_busy", None)
+        if busy is not None and busy.in_flight():
+            raise RuntimeError("enable_fp8_kv: a ContinuousBatcher holds requests in flight on this decoder's slots, whose caches would change "
+                               "format under them: drain it (run()) first")
+        if on and self.kv8 is None:
+            self.kv8 = [ops.kv8_alloc((), self.nkv, self.max_seq_len, self._dev) for _ in range(self.n_layers)]
+        if not on:
+            self.kv8 = None                          # freed with the switch (allocated again by the next enable)
+        self._fp8_kv = bool(on)
+        self._invalidate_graphs()
+        self._bb = None                              # the slot caches are in the other format: the next batched call allocates them again
+        self.pos = 0
+        self.cache_epoch += 1
+        return self
+
+    def _quant_rows(self, kcache, vcache, kv8, n):
+        """Rows [0, n) of every layer's 16-bit caches (a prefill's) -> the fp8 caches kv8 (per layer (k8, v8, ks, vs))."""
+        for li in range(self.n_layers):
+            ops.kv_quant(kcache[li], vcache[li], kv8[li], 0, n)
 
     def _make_w8(self):
         """The fp8 copies of the packed projections (shared by the decode and the prefill switch).  The stage descriptor is rebuilt with
@@ -326,12 +377,16 @@ class HipMistralDecoder(nn.Module):
             ops.llm_prefill(self._stage_desc()[0], x, out, fp8=self.prefill_fp8)
             self.pos = S
             self.last_hidden = None
+            if self._fp8_kv:
+                self._quant_rows(self.kcache, self.vcache, self.kv8, S)
             return out
         # operator by operator: the RMSNorm rides in the q/k/v and gate/up GEMMs (weights.fold_norm), or the fp8 matrix pipe (vl2_stage.inc)
         f = _W8A8(self) if self.prefill_fp8 else _Tiled(self)
         x = self._rows(f, x, [(0, S, 0, kcache, vcache)], () if return_all_logits else (out,))
         self.pos = S
         self.last_hidden = x
+        if self._fp8_kv and cache is None:         # the decode steps read the fp8 cache: the prefill's rows, quantised once
+            self._quant_rows(kcache, vcache, self.kv8, S)
         if return_all_logits:
             return ops.gemm(ops.rmsnorm(x, self.w["norm_w"], self.eps), self.w["lm_head"], out_f32=True)
         return out
@@ -347,6 +402,8 @@ class HipMistralDecoder(nn.Module):
         start_pos + n.  Few rows: the skinny-M projections (RMSNorm as its own launch, like the batched decode step) and the append
         attention; otherwise the prefill's tiled GEMMs and vl2_attn_fwd."""
         _lib.check_elem(self._elem, type(self).__name__)
+        if self._fp8_kv:
+            raise NotImplementedError(self.FP8_KV_EXTEND_MSG)
         if self.tp > 1 or self.tp_always_reduce:
             raise NotImplementedError("extend: single-rank decoders only")
         if self.prefill_fp8:
@@ -389,12 +446,18 @@ class HipMistralDecoder(nn.Module):
         """Enqueue one decode step for the token in self.tok: embed -> 32 x {qkv GEMV (+RMSNorm), RoPE+append+attention,
         o GEMV (+res), gate/up GEMV (+RMSNorm, SwiGLU), down GEMV (+res)} -> lm_head GEMV (+final RMSNorm) into self.logits, on the
         16-bit weights, their fp8 copies (enable_fp8_decode) or their MXFP4 copies (enable_mxfp4_decode; lm_head 16-bit).  dyn=True reads the position from self.state[0] on the device
-        (hipGraph-replayable); no allocation either way."""
+        (hipGraph-replayable); no allocation either way.  With enable_fp8_kv the attention appends to and reads the fp8 cache (self.kv8); the
+        16-bit cache is not touched."""
         b = self._b
         pos_dev = self.state[0:1] if dyn else None
+        if self._fp8_kv:
+            self._fp8_kv_refusals()                  # (tp_always_reduce can be set after the switch)
         ops.embed_rows(self.tok, self.w["embed"], b["x0"])
 
         def attend(li, qkv, o):
+            if self._fp8_kv:
+                return ops.attn_decode_kv8(qkv, self.kv8[li], self.cos_t, self.sin_t, self.partial, o, self.nh, self.nkv, self.pos,
+                                           self.hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
             ops.attn_decode(qkv, self.kcache[li], self.vcache[li], self.cos_t, self.sin_t, self.partial, o, self.nh, self.nkv,
                             self.pos, self.hd ** -0.5, pos_dev=pos_dev, ctx_cap=self.max_seq_len)
         self._tokens(_Gemv(self, self.decode_format, batched=False), attend, b["x0"][0], b["x1"], b["qkv"], b["o"], b["a"], self.logits)
@@ -429,7 +492,7 @@ class HipMistralDecoder(nn.Module):
             if sampler is not None:                           # (the stage call opens with its own argmax: the sampled step is the operator sequence)
                 ops.sample_token(self.logits, self.tok, self.u_buf, sampler[0], sampler[1], sampler[2], hist=self.hist, state=self.state)
                 self._decode_kernels(dyn=True)
-            elif self._use_stage() and not self.decode_mxfp4:        # (the stage call knows the 16-bit and the fp8 weights)
+            elif self._use_stage() and not self.decode_mxfp4 and not self._fp8_kv:        # (the stage call knows the 16-bit and the fp8 weights, 16-bit KV)
                 d, _, ws = self._stage_desc()
                 ops.llm_decode_step(d, self.logits, self.tok, self.state, self.hist, self.partial, ws, fp8=self.decode_fp8)
             else:
@@ -574,9 +637,16 @@ class HipMistralDecoder(nn.Module):
             ops.attach_workspace(self._dev)          # fp32 partial sums of the skinny-M GEMMs of a large-batch decode step
         bf = dict(dtype=_lib.elem_dtype(), device=self._dev)
         smax, I = self.max_seq_len, self.cfg["llm"]["intermediate_size"] // self.tp
+        if self._fp8_kv:         # the slots in fp8 ONLY (per layer (k8, v8, ks, vs) with a leading slot dimension) + one sequence's 16-bit staging
+            self._fp8_kv_refusals()                  # cache, which a request's prefill fills before its rows are quantised into its slot
+            caches = dict(kv8=[ops.kv8_alloc((B,), self.nkv, smax, self._dev) for _ in range(self.n_layers)],
+                          stage=([torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
+                                 [torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)]))
+        else:
+            caches = dict(k=[torch.zeros((B, self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
+                          v=[torch.zeros((B, self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)])
         self._bb = dict(
-            B=B, k=[torch.zeros((B, self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
-            v=[torch.zeros((B, self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
+            B=B, **caches,
             partial=torch.empty((B * self.nh * ((smax + 63) // 64) * 130,), dtype=torch.float32, device=self._dev),
             x0=torch.empty((B, self.D), **bf), x1=torch.empty((B, self.D), **bf), qkv=torch.empty((B, (self.nh + 2 * self.nkv) * self.hd), **bf),
             o=torch.empty((B, self.nh * self.hd), **bf), a=torch.empty((B, I), **bf),
@@ -587,6 +657,18 @@ class HipMistralDecoder(nn.Module):
             samp_p=torch.ones((B,), dtype=torch.float32, device=self._dev), u=torch.zeros((B, smax + 1), dtype=torch.float32, device=self._dev),
             sstep=torch.zeros((B,), dtype=torch.int32, device=self._dev))
         return self._bb
+
+    def prefill_slot(self, slot, x, logits_out):
+        """Prefill one request (inputs_embeds x [S, D]) into batch slot `slot`: rows [0, S) of its caches, the last row's fp32 logits in
+        logits_out.  fp8 KV: through the 16-bit staging cache, whose rows [0, S) are then quantised into the slot.  The decoder's own
+        single-sequence position is left alone."""
+        bb, own_pos = self._bb, self.pos
+        if self._fp8_kv:
+            self.prefill(x, cache=bb["stage"], logits_out=logits_out)
+            self._quant_rows(*bb["stage"], [tuple(t[slot] for t in kv8) for kv8 in bb["kv8"]], x.shape[0])
+        else:
+            self.prefill(x, cache=([k[slot] for k in bb["k"]], [v[slot] for v in bb["v"]]), logits_out=logits_out)
+        self.pos = own_pos
 
     PREFILL_GROUP_TOKENS = 8192   # rows prefilled in one pass (activation scratch: ~0.6 GB at 7B widths)
     GEMM_BATCH = 5      # from this many sequences on, the decode step runs its projections on MFMA (M = sequences)
@@ -601,8 +683,12 @@ class HipMistralDecoder(nn.Module):
         With enable_fp8_decode the same step streams the fp8 copies (W8A16): the multi-row fp8 GEMV below GEMM_BATCH (a row is bit-identical
         to the single-sequence fp8 step), the fp8 skinny-M kernel from GEMM_BATCH on, in calls of at most 64 rows (bit-identical to the 16-bit
         skinny-M step on the dequantised weights).  With enable_mxfp4_decode: the same two paths on the MXFP4 copies, with the same guarantees
-        against the solo MXFP4 step and the dequantised weights; lm_head on the 16-bit kernels."""
+        against the solo MXFP4 step and the dequantised weights; lm_head on the 16-bit kernels.
+        With enable_fp8_kv the attention of every form above runs on the slots' fp8 caches (one vl2_attn_decode_kv8_batched launch per layer):
+        a row's attention is bit for bit the single-sequence fp8-KV step's."""
         bb = self._bb
+        if self._fp8_kv:
+            self._fp8_kv_refusals()                  # (tp_always_reduce can be set after the slots exist)
         x = bb["x0"][:nb]
         ops.embed_rows(bb["tok"][:nb], self.w["embed"], x)
         if nb >= self.GEMM_BATCH:
@@ -614,6 +700,9 @@ class HipMistralDecoder(nn.Module):
             f = _Gemv(self, self.decode_format, batched=True)
 
         def attend(li, qkv, o):
+            if self._fp8_kv:
+                return ops.attn_decode_kv8_batched(qkv, tuple(t[:nb] for t in bb["kv8"][li]), self.cos_t, self.sin_t, bb["partial"], o,
+                                                   self.nh, self.nkv, bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
             ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, self.nh, self.nkv,
                                     bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
         self._tokens(f, attend, x, bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb], bb["logits"][:nb])
@@ -663,7 +752,10 @@ class HipMistralDecoder(nn.Module):
         sampler = (temperature, top_k, top_p[, generator]): HF `_sample` with do_sample=True for every request -- ONE ops.sample_tokens launch per
         step over all requests in place of their argmaxes (request b draws from its own row u[b, step] of uniform numbers, generated request by
         request from the generator, so request 0's stream is the one a single-sequence `generate` with the same seed would use; its token is the
-        one ops.sample_token gives on its row); replayed from its own captured graph like the greedy step."""
+        one ops.sample_token gives on its row); replayed from its own captured graph like the greedy step.
+        With enable_fp8_kv the slots hold fp8 rows only, so the requests are prefilled ONE AFTER ANOTHER through the single 16-bit staging
+        cache and quantised into their slots (bit-identical to the grouped prefill); what it costs is the fuller GEMM
+        grids of the grouped prefill: short prompts run their projections at a smaller M each."""
         nb = len(inputs_embeds_list)
         if use_graph is None:
             use_graph = self._dev.type == "cuda" and self.tp == 1
@@ -682,7 +774,7 @@ class HipMistralDecoder(nn.Module):
             bb["u"][:nb, :n_u].copy_(u_rows); bb["sstep"][:nb].zero_()
         # prompts are prefilled together in groups of <= PREFILL_GROUP_TOKENS rows (bit-identical to one by one)
         lens, group, gtok = [], [], 0
-        caches = [([k[b] for k in bb["k"]], [v[b] for v in bb["v"]]) for b in range(nb)]
+        caches = None if self._fp8_kv else [([k[b] for k in bb["k"]], [v[b] for v in bb["v"]]) for b in range(nb)]
 
         def flush():
             if group:
@@ -691,6 +783,12 @@ class HipMistralDecoder(nn.Module):
                 group.clear()
 
         for b, xb in enumerate(inputs_embeds_list):
+            if self._fp8_kv:                         # one by one through the staging cache
+                if xb.shape[0] > self.max_seq_len:
+                    raise ValueError(f"sequence length {xb.shape[0]} exceeds the KV cache ({self.max_seq_len})")
+                self.prefill_slot(b, xb, bb["logits"][b])
+                lens.append(xb.shape[0])
+                continue
             if gtok + xb.shape[0] > self.PREFILL_GROUP_TOKENS:
                 flush()
                 gtok = 0
@@ -760,6 +858,10 @@ class HipMixtralDecoder(HipMistralDecoder):
 
     def enable_mxfp4_decode(self, on=True):
         raise NotImplementedError("MoE (mixtral) decoder: MXFP4 weights not built")
+
+    def enable_fp8_kv(self, on=True):
+        raise NotImplementedError("MoE (mixtral) decoder: the fp8 KV cache is not built for it (its step runs the MoE GEMVs on the 16-bit "
+                                  "cache): keep the 16-bit cache")
 
     def prefill_batch(self, xs, caches, logits_out):
         raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")

@@ -309,6 +309,8 @@ class VideoLLaMA2Hip(nn.Module):
             raise NotImplementedError("prefix_cache=True: batch 1 only")
         if self.decoder.tp > 1:
             raise NotImplementedError("prefix_cache=True: single-rank decoders only (extend is not built for tensor parallelism)")
+        if getattr(self.decoder, "fp8_kv", False):
+            raise NotImplementedError(self.decoder.FP8_KV_EXTEND_MSG)
         ids = inputs[0].detach().cpu()
         if attention_mask is not None:                           # batch 1, right-padded: the real tokens are the leading ones
             m = attention_mask.detach().cpu().bool()[0]
@@ -394,6 +396,15 @@ class VideoLLaMA2Hip(nn.Module):
                 row += 1
         flush(row)
         return emb
+
+    def enable_fp8_kv(self, on=True):
+        """OPTIONAL arithmetic, never the default: the decoder keeps its decode KV cache in fp8 (`HipMistralDecoder.enable_fp8_kv`: half the
+        attention's bytes per step, 0.52 x the slot memory of the batched paths).  It stands next to the decode-weight switches
+        `self.decoder.enable_fp8_decode()` / `enable_mxfp4_decode()` and combines with either.  generate(prefix_cache=True), tensor-parallel
+        decoders, Mixtral and head_dim != 128 refuse it."""
+        self.decoder.enable_fp8_kv(on)
+        self._prefix_rec = None                      # the resident rows a prefix-cache call recorded are gone
+        return self
 
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None):
         """Continuous batching over this model (serving.ModelBatcher): submit (input_ids, images) requests at any time, `step()`

@@ -534,6 +534,61 @@ def attn_decode_batched(qkv, kcache, vcache, cos_t, sin_t, partial, out, nh, nkv
     return out
 
 
+def kv8_alloc(shape_prefix, nkv, smax, device):
+    """One layer's fp8 KV cache (include/vl2hip.h, csrc/k_kv8.h) as (k8, v8, ks, vs): e4m3fn codes uint8 [*shape_prefix, nkv, smax, 128] and
+    fp32 row scales [*shape_prefix, nkv, smax] (scale 1 on the empty rows, so that every row always dequantises to finite numbers)."""
+    codes = lambda: torch.zeros((*shape_prefix, nkv, smax, 128), dtype=torch.uint8, device=device)
+    scales = lambda: torch.ones((*shape_prefix, nkv, smax), dtype=torch.float32, device=device)
+    return codes(), codes(), scales(), scales()
+
+
+def _chk_kv8(kv8):
+    k8, v8, ks, vs = kv8
+    for t, dt, name in ((k8, torch.uint8, "k8"), (v8, torch.uint8, "v8"), (ks, torch.float32, "ks"), (vs, torch.float32, "vs")):
+        _chk(t, dt, name)
+    if k8.shape[-1] != 128 or v8.shape != k8.shape or ks.shape != k8.shape[:-1] or vs.shape != ks.shape:
+        raise ValueError(f"fp8 KV cache: need codes [.., nkv, smax, 128] and scales [.., nkv, smax], got {tuple(k8.shape)}, {tuple(v8.shape)}, "
+                         f"{tuple(ks.shape)}, {tuple(vs.shape)}")
+    if not (k8[0:1].is_contiguous() and v8[0:1].is_contiguous() and ks[0:1].is_contiguous() and vs[0:1].is_contiguous()):
+        raise ValueError("fp8 KV cache: a sequence's codes and scales must be contiguous")
+    return k8, v8, ks, vs
+
+
+def kv_quant(kcache, vcache, kv8, p0, p1):
+    """include/vl2hip.h vl2_kv_quant: rows [p0, p1) of one sequence's 16-bit caches [nkv, smax, 128] -> e4m3fn codes and power-of-two row
+    scales at the same rows of kv8 = (k8, v8, ks, vs) (uint8 [nkv, smax, 128] x 2, fp32 [nkv, smax] x 2).  Other rows are not written."""
+    _chk(kcache, _lib.elem_dtype(), "kcache"); _chk(vcache, _lib.elem_dtype(), "vcache")
+    k8, v8, ks, vs = _chk_kv8(kv8)
+    if k8.dim() != 3 or kcache.shape != k8.shape or vcache.shape != k8.shape or not (kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError(f"kv_quant: need contiguous 16-bit caches of the codes' shape {tuple(k8.shape)}, got {tuple(kcache.shape)}, {tuple(vcache.shape)}")
+    nkv, smax, _ = k8.shape
+    _lib.call("vl2_kv_quant", _p(kcache), _p(vcache), _p(k8), _p(v8), _p(ks), _p(vs), nkv, smax, int(p0), int(p1), _stream())
+    return kv8
+
+
+def attn_decode_kv8(qkv, kv8, cos_t, sin_t, partial, out, nh, nkv, pos, scale, pos_dev=None, ctx_cap=0):
+    """include/vl2hip.h vl2_attn_decode_kv8: `attn_decode` on one sequence's fp8 cache kv8 = (k8, v8, ks, vs): the new token's K / V rows are
+    quantised into row `pos` (or *pos_dev), the attention reads codes and scales."""
+    k8, v8, ks, vs = _chk_kv8(kv8)
+    if k8.dim() != 3:
+        raise ValueError(f"attn_decode_kv8: one sequence's cache [nkv, smax, 128], got {tuple(k8.shape)}")
+    _lib.call("vl2_attn_decode_kv8", _p(qkv), _p(k8), _p(v8), _p(ks), _p(vs), _p(cos_t), _p(sin_t), _p(partial), _p(out), nh, nkv,
+              k8.shape[1], int(pos), _p(pos_dev), int(ctx_cap), float(scale), _stream())
+    return out
+
+
+def attn_decode_kv8_batched(qkv, kv8, cos_t, sin_t, partial, out, nh, nkv, pos_dev, ctx_cap, scale):
+    """include/vl2hip.h vl2_attn_decode_kv8_batched: `attn_decode_batched` on the slots' fp8 caches kv8 = (k8, v8, ks, vs) with a leading
+    slot dimension: codes [B, nkv, smax, 128], scales [B, nkv, smax]."""
+    k8, v8, ks, vs = _chk_kv8(kv8)
+    B = qkv.shape[0]
+    if k8.dim() != 4 or k8.shape[0] != B or v8.stride(0) != k8.stride(0) or vs.stride(0) != ks.stride(0):
+        raise ValueError(f"attn_decode_kv8_batched: need the {B} sequences' caches [B, nkv, smax, 128] with equal strides, got {tuple(k8.shape)}")
+    _lib.call("vl2_attn_decode_kv8_batched", _p(qkv), _p(k8), _p(v8), _p(ks), _p(vs), _p(cos_t), _p(sin_t), _p(partial), _p(out), B,
+              qkv.stride(0), k8.stride(0), ks.stride(0), out.stride(0), nh, nkv, k8.shape[2], _p(pos_dev), int(ctx_cap), float(scale), _stream())
+    return out
+
+
 _APPEND_WS = {}
 
 

@@ -35,7 +35,10 @@ class ContinuousBatcher:
     use_graph (default: on a GPU): one captured hipGraph per occupancy (highest occupied slot + 1).
     fp8 / MXFP4 decode weights (decoder.enable_fp8_decode() / enable_mxfp4_decode()): the steps stream those copies, with the same guarantees
     against the solo decode on the same copies.  Toggling them with requests in flight is allowed: the toggle drops the captured step graphs, the next step runs (and captures) every
-    slot on the weights then selected, and the decoder's cache_epoch is bumped as for any toggle."""
+    slot on the weights then selected, and the decoder's cache_epoch is bumped as for any toggle.
+    fp8 KV cache (decoder.enable_fp8_kv()): the slots hold fp8 rows only (0.52 x the memory), a request is prefilled into the decoder's 16-bit
+    staging cache and quantised into its slot, and the steps attend on the fp8 rows -- a request's tokens equal its solo fp8-KV decode.  That
+    switch changes the slots' format, so the decoder refuses it while requests are in flight."""
 
     def __init__(self, decoder, max_slots=4, eos_token_id=None, use_graph=None):
         if decoder.tp > 1:
@@ -89,10 +92,7 @@ class ContinuousBatcher:
             if self.slots[slot] is not None:
                 continue
             r = self.waiting.popleft()
-            cache = ([k[slot] for k in bb["k"]], [v[slot] for v in bb["v"]])
-            own_pos = dec.pos                                                     # the decoder's own single-sequence state is not ours
-            dec.prefill(r.x, cache=cache, logits_out=bb["logits"][slot])          # fills rows [0, S) of the slot's cache
-            dec.pos = own_pos
+            dec.prefill_slot(slot, r.x, bb["logits"][slot])                       # rows [0, S) of the slot's cache (fp8 KV: quantised from the staging cache)
             bb["pos"][slot:slot + 1].fill_(r.x.shape[0])
             T, k, p = r.sampler if r.sampler is not None else (0.0, 0, 1.0)                # temperature 0: a greedy slot
             bb["samp_T"][slot:slot + 1].fill_(T); bb["samp_k"][slot:slot + 1].fill_(k); bb["samp_p"][slot:slot + 1].fill_(p)
@@ -108,9 +108,11 @@ class ContinuousBatcher:
         """Admit, run one step, retire.  Returns {request id: new token} for the requests that produced a token."""
         self.dec._ensure_batch(self.max_slots, owner=self)     # raises if ANOTHER batcher owns the slots with requests in flight
         self.dec._bb_busy = self                               # from here on generate_batch / a second batcher are refused while we hold requests
-        if self.dec._bb is not self.bb:       # a larger generate_batch() on the same decoder reallocated the slot buffers (and caches)
-            raise RuntimeError("the decoder's batch buffers were reallocated while requests were in flight: use one batcher per decoder "
-                               "and do not call generate_batch() with more sequences than max_slots on it")
+        if self.dec._bb is not self.bb:       # the slot buffers (and caches) were reallocated: a larger generate_batch() on this decoder, enable_fp8_kv
+            if any(r is not None for r in self.slots):
+                raise RuntimeError("the decoder's batch buffers were reallocated while requests were in flight: use one batcher per decoder "
+                                   "and do not call generate_batch() with more sequences than max_slots on it")
+            self.bb = self.dec._bb            # no slot is occupied, so no request's rows were lost: go on in the new buffers
         self._admit()
         occupied = [s for s, r in enumerate(self.slots) if r is not None]
         if not occupied:
