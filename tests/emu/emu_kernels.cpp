@@ -42,7 +42,7 @@ static int g_mfma16_mode = 0;       // variants 17 / 18: the lab orders of gemm9
 static int g_mfma16_tile = 0;       // 256 / 224 / 192 with VL2_GEMM_MFMA16: the one-round 128 x 128 / fill-the-round tiles of the 16 x 16 x 32 set (k_gemm9.h, k_gemm7.h)
 static bool g_mfma16 = false;       // variant 16 / VL2_GEMM_MFMA16: the 256 x 256 ping-pong tile on the 16 x 16 x 32 matrix instruction (k_gemm9.h)
 static bool g_weave4 = false;       // VL2_GEMM_WEAVE4: the 256-/192-row ping-pong bodies with the woven LDS-DMA issue
-static bool g_need_fin = false;     // a GEMM path without the producer-side finalize ran: append the row_norm_finalize launch (vl2_abi.hip GemmCtl.fin)
+static bool g_need_fin = false;     // a GEMM path without the producer-side finalize ran: append the row_norm_finalize launch (gemm_plan.h GemmLaunch::needs_finalize)
 static bool g_gemm6_dynamic = false;       // gemm6: tiles handed out through the counter block (variants 70 / 71 = 60 / 61 dynamic)
 template <int ACT, bool SW, bool F32, bool G>
 static void run_gemm(GemmArgs a) {
@@ -61,7 +61,7 @@ static void run_gemm(GemmArgs a) {
             }
         }
         if (g_mfma16 && g_mfma16_mode == 0 && a.M > 256 && a.M % 256 != 0 && a.N % 256 == 0) {
-            // vl2_abi.hip launch_gemm: a row-split call on the 16 x 16 x 32 instruction is ONE mixed launch (k_gemm9.h gemm_mix16_bf16_kernel)
+            // gemm_plan.h gemm_plan_rows: a row-split call on the 16 x 16 x 32 instruction is ONE mixed launch (k_gemm9.h gemm_mix16_bf16_kernel)
             const int M1 = (a.M / 256) * 256;
             GemmArgs big = a, tail = a;
             big.M = M1; big.tiles_m = M1 / 256; big.tiles_n = a.N / 256;
@@ -77,7 +77,7 @@ static void run_gemm(GemmArgs a) {
             return;
         }
         if (g_mfma16) {
-            if (g_mfma16_mode != 0 && a.row_norm_out) g_need_fin = true;       // only the shipped form (MODE 0) finalizes its rows itself (vl2_abi.hip launch_gemm)
+            if (g_mfma16_mode != 0 && a.row_norm_out) g_need_fin = true;       // only the shipped form (MODE 0) finalizes its rows itself (gemm_plan.h gemm_plan_rows)
             a.tiles_m = (a.M + 255) / 256; a.tiles_n = a.N / 256;
             if (g_mfma16_mode == 1) emu::launch(dim3(a.tiles_m * a.tiles_n), dim3(512), [=] { gemm9_bf16_kernel<SW, 1>(a); });
             else if (g_mfma16_mode == 2) emu::launch(dim3(a.tiles_m * a.tiles_n), dim3(512), [=] { gemm9_bf16_kernel<SW, 2>(a); });
@@ -104,7 +104,7 @@ static void run_gemm(GemmArgs a) {
     if constexpr (!G) {
         if (g_gemm_variant == 4 && a.N % 256 == 0) {
             a.tiles_m = (a.M + 127) / 128; a.tiles_n = a.N / 256;
-            if constexpr (!F32) {        // vl2_abi.hip want_tr_epilogue: no residual -> register-resident C^T epilogue
+            if constexpr (!F32) {        // gemm_plan.h want_tr_epilogue: no residual -> register-resident C^T epilogue
                 if (a.res == nullptr) { emu::launch(dim3(a.tiles_m * a.tiles_n), dim3(512), [=] { gemm3_bf16_kernel<ACT, SW, false, true>(a); }); return; }
             }
             emu::launch(dim3(a.tiles_m * a.tiles_n), dim3(512), [=] { gemm3_bf16_kernel<ACT, SW, F32>(a); });
@@ -145,7 +145,7 @@ static void run_gemm(GemmArgs a) {
         }
     }
     if constexpr (!G && !F32) {
-        if (g_gemm_variant == 24 && a.N % 256 == 0 && a.M > 256) {   // the row-split call as ONE mixed launch (vl2_abi.hip launch_gemm): big tiles on
+        if (g_gemm_variant == 24 && a.N % 256 == 0 && a.M > 256) {   // the row-split call as ONE mixed launch (gemm_plan.h gemm_plan_rows): big tiles on
             const int M1 = (a.M / 256) * 256 == a.M ? a.M - 256 : (a.M / 256) * 256;      // the leading whole 256-row tiles, 128x128 8-wave tiles on the rest
             GemmArgs big = a, tail = a;
             big.M = M1; big.tiles_m = M1 / 256; big.tiles_n = a.N / 256;

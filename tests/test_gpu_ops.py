@@ -97,7 +97,8 @@ def test_gemm_pingpong_variant_is_bit_identical(ops, M, N, K):
         ops.set_gemm_variant(0)
 
 
-@pytest.mark.parametrize("M,N,K", [(1621, 4096, 14336), (1621, 4096, 4096), (1521, 4096, 4096), (1400, 4096, 1024), (225, 128, 64), (3000, 1024, 2048)])
+@pytest.mark.parametrize("M,N,K", [(1621, 4096, 14336), (1621, 4096, 4096), (1521, 4096, 4096), (1400, 4096, 1024), (225, 128, 64), (3000, 1024, 2048),
+                                   (6913, 896, 1024)])        # (the last: the smallest shape the automatic choice gives the 224-row tile, csrc/gemm_plan.h)
 def test_gemm_fill_round_kernel_is_bit_identical(ops, M, N, K):
     """csrc/k_gemm7.h (224 x 128 / 192 x 128 tiles, knobs 224 / 192; the automatic choice for the decoder's o / down projections at
     S = 1621 and the connector's GEMMs on 1521 positions): same K order and epilogue arithmetic as the 128 x 128 kernel -> the same bits,

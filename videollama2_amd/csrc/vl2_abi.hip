@@ -31,6 +31,7 @@ static constexpr bool kLab = false;
 #include "k_sample.h"
 #include "k_skinny.h"
 #include "k_skinny_fp8.h"
+#include "gemm_plan.h"
 #include "skinny_plan.h"
 #include "k_mxfp4.h"
 #include "k_stc.h"
@@ -73,14 +74,18 @@ static void lds_attr(int bytes) {
         done.fetch_or(bit, std::memory_order_release);
     }
 }
+// the opt-in and the launch of a kernel instance with `lds` bytes of dynamic LDS
+template <auto Kern, class... Args>
+static void launch(dim3 grid, dim3 block, int lds, hipStream_t s, const Args&... args) {
+    lds_attr<Kern>(lds);
+    hipLaunchKernelGGL(Kern, grid, block, lds, s, args...);
+}
 
 extern "C" int32_t vl2_version(void) { return VL2_ABI_VERSION; }
 extern "C" const char* vl2_elem_name(void) { return VL2_ELEM_NAME; }
 extern "C" const char* vl2_last_error_string(void) { return g_err; }
 
-#define SK_GRID 512                  // persistent stream-K workgroups: 2 per CU
-#define SPLITK_MAX_WG 1024           // split-K: at most this many (tile, split) workgroups -> 64 MiB of fp32 partials
-#define SPLITK_MAX_TILES 192         // split-K only when the plain grid leaves most of the 512 resident slots empty
+// (SK_GRID, SPLITK_MAX_WG, SPLITK_MAX_TILES: gemm_plan.h)
 // workspace layout: [SPLITK_MAX_WG][64][256] fp32 partial tiles (stream-K uses the first SK_GRID) | stream-K flags
 // [SK_GRID + 1] | split-K tile counters [SPLITK_MAX_TILES] (zero when allocated, re-armed by the kernel itself)
 #define SK_FLAGS_OFF ((int64_t)SPLITK_MAX_WG * 64 * 256 * 4)
@@ -101,250 +106,12 @@ extern "C" int32_t vl2_fill_zero(void* p, int64_t bytes, void* stream) {
     return launched("vl2_fill_zero");
 }
 
-// per-call launch controls (vl2_gemm_desc: ws / ws_bytes / variant / VL2_GEMM_SPLITK) -- nothing of this is process state
-struct GemmCtl {
-    void* ws;
-    int64_t ws_bytes;
-    int variant;
-    bool splitk;
-    bool no_persist = false;       // variant 24: the automatic choice without the persistent form
-    bool persist = false;          // VL2_GEMM_PERSISTENT: the automatic choice may take the persistent form
-    bool no_mix = false;           // VL2_GEMM_NO_MIX
-    bool no_fill = false;          // VL2_GEMM_NO_FILL
-    bool weave = false;            // VL2_GEMM_WEAVE
-    bool no_weave4 = false;        // VL2_GEMM_NO_WEAVE4: the 192-row tiles with the load-phase issue of rounds 3-4 (A/B)
-    bool mfma16 = false;           // VL2_GEMM_MFMA16 / variant 16: the 256 x 256 ping-pong kernel on v_mfma_f32_16x16x32_bf16 (k_gemm9.h; other bits)
-    bool weave4 = false;           // VL2_GEMM_WEAVE4: the 256 x 256 / 192 x 256 ping-pong bodies issue their LDS-DMA from the matrix phases (k_gemm.h gemm4_body WEAVE4)
-    bool* fin = nullptr;           // set to true by a launch path whose kernel has no producer-side finalize (gemm_rows_ticket): vl2_gemm then
-                                   // appends the row_norm_finalize launch itself, so `row_norm_out` is filled whichever kernel ran
-};
-
 // ------------------------------------------------------------------------------------------------ GEMM
-// stream-K form: measured 0.5-0.6x of the plain grid on this workload's shapes (per-tile prologue/epilogue of the persistent
-// workgroups, ~15 us of partial-tile exchange, worse L2 locality of strided tile ownership) -> only on explicit request.
-static bool want_stream_k(const GemmArgs& a, const GemmCtl& c) { return c.ws && c.variant == 2 && !a.norm && !a.stats_out; }
+// Which kernel form a call gets is decided in gemm_plan.h (plain host C++, held by tests/test_gemm_plan_host.py); what follows turns a planned
+// launch into its instantiation.  The plan's tile sizes are the kernels':
+static_assert(GEMM_BM == 128 && GEMM_BN == 128 && GEMM_BK == 64 && GEMM3_BM == 128 && GEMM3_BN == 256 && GEMM4_BM == 256 && GEMM4_BN == 256 && GEMM4_BK == 32 &&
+              GEMM7_BN == 128 && GEMMS_BM == 64 && GEMMS_BN == 64, "gemm_plan.h restates the tile sizes of k_gemm.h / k_gemm7.h");
 
-// Tile-shape choice (auto): expected efficiency = how full the last round of resident workgroups is x rows wasted by the
-// M edge x the kernel's measured rate on well-quantised shapes (128x128 two-barrier kernel 1.0, 128x256 ping-pong 1.07,
-// 256x256 ping-pong 1.2: profiles/r01_gemm_experiments.md).  Fitted to the measured shapes of the T=16 workload: the LLM
-// o/gate-up/down projections and the STC 4096x4096 convs take 128x256, ViT qkv/wo/fc2 and the LLM qkv take 256x256,
-// short-K GEMMs (STC b1) stay on 128x128.  Returns 1, 4 (gemm3), 8 (gemm4) or 12 (gemm4 on 192-row tiles).
-static int choose_gemm_kernel(const GemmArgs& a, double* eff = nullptr) {
-    if (eff) *eff = 0.0;
-    if (a.N % 256) return 1;
-    // at most one 128x128 tile per CU: a bigger tile only halves the CUs in use and doubles the latency of the single round
-    // (measured, T=8: 845x4096x4096 44.6 us here vs 50.2 us on 128x256; 945x4096x4096 47.2 vs 51.2)
-    if ((long)((a.M + 127) / 128) * (a.N / 128) <= 256) return 1;
-    const auto fill = [](double rounds) { return rounds / (double)(long)(rounds + 0.999999); };
-    const double m128 = (double)a.M / (((a.M + 127) / 128) * 128.0), m256 = (double)a.M / (((a.M + 255) / 256) * 256.0);
-    const double e1 = fill((double)((a.M + 127) / 128) * (a.N / 128) / 512.0) * m128;           // 2 WG/CU
-    const double e3 = fill((double)((a.M + 127) / 128) * (a.N / 256) / 256.0) * m128 * 1.07;    // 1 WG/CU
-    const double e4 = fill((double)((a.M + 255) / 256) * (a.N / 256) / 256.0) * m256 * 1.2;     // 1 WG/CU
-    int best = 1;
-    double eb = 1.03 * e1;
-    if (a.K >= 2048 && e3 > eb) { best = 4; eb = e3; }
-    if (a.K >= 512 && e4 > eb) { best = 8; eb = e4; }
-    // the 256x256 kernel on 192-row tiles (variant 12): the same rate per FLOP over whole rounds (sq 4096^3: 85 us per round of 192-row
-    // tiles against 117), a little less in practice (fc1 at 3.06 rounds 105.9 us vs 95.4 on 256 rows) -> 1.13.  Takes the shapes whose
-    // 256-row grid leaves a round badly filled: ViT out_proj / fc2 at 16 frames (148 -> 196 tiles: 30.7 -> 28.9 us, 84.6 -> 81.3), the
-    // LLM q/k/v at S = 1621 (168 -> 216 tiles: 84.0 -> 81.2), the STC K = 1024 conv (576 = 2.25 rounds -> 768 = 3.0: 87.6 -> 82.2).
-    // scripts/ubench/gemm_lab.hip (bit-identical, hash-checked) and scripts/kernel_bench.py, profiles/r03_gemm_lab_t192.txt
-    const double m192 = (double)a.M / (((a.M + 191) / 192) * 192.0);
-    const double e5 = fill((double)((a.M + 191) / 192) * (a.N / 256) / 256.0) * m192 * 1.13;
-    if (a.K >= 512 && e5 > eb * 1.02) { best = 12; eb = e5; }
-    // ... and on 160-row tiles (variant 10, round 6: the 192-row tile without group 1's third row block): ONE-round grids only, where a finer tile
-    // shortens the single round -- ViT out_proj / fc2 at 16 frames: 196 tiles of 192 rows (77 % of the CUs) -> 232 tiles of 160 rows (91 %).  Rate 1.08:
-    // a SIMD issues 20 MFMAs per slab behind the same load phases (24 on 192 rows).
-    // MEASURED AND NOT TAKEN (profiles/r06_tile160_bench.txt, interleaved on one box): fc2 9232 x 1024 x 4096 79.2 us on 192 rows, 82.7 on 160; out_proj 30.4 vs
-    // 30.9; 18464 rows: 163.5 vs 166.5.  A one-round grid at 77 % of the CUs is NOT 77 % of the chip: the part runs at its power limit, and 196 workgroups at a
-    // higher clock do what 232 do at a lower one -- filling the round buys nothing where watts, not CUs, are the budget.  The tile stays a lab form (variant 10).
-    if (eff) *eff = best == 1 ? e1 : eb;
-    return best;
-}
-
-// gemm7 (k_gemm7.h): 224 x 128 / 192 x 128 tiles for GEMMs that are ONE round of workgroups whatever the tile -- 0 = not this call, else R1
-// (3 = 224 rows, 2 = 192 rows).  Same efficiency model as choose_gemm_kernel: fill of the last round x rows wasted at the M edge x the
-// kernel's rate relative to the 128x128 kernel (GEMM7_RATE, measured: profiles/r05_experiments.md).  Only where the 128x128 grid is
-// more than one tile per CU (below that the one-round 128x128 / 64x64 kernels own the shape) and the K loop is long enough to pay for
-// the image epilogue.
-#define GEMM7_RATE 0.88
-static int choose_gemm7(const GemmArgs& a, bool gather) {
-    if (a.N % GEMM7_BN || a.K < 1024 || a.out_grp > 0 || a.res_row_mod > 0) return 0;
-    const long t128 = (long)((a.M + 127) / 128) * (a.N / 128);
-    if (t128 <= 256) return 0;
-    const auto fill = [](double rounds) { return rounds / (double)(long)(rounds + 0.999999); };
-    double eb = 0.0;
-    if (gather) eb = fill((double)t128 / 512.0) * ((double)a.M / (((a.M + 127) / 128) * 128.0));     // the gathered form has the 128x128 kernel only
-    else choose_gemm_kernel(a, &eb);
-    int best = 0;
-    for (int r1 = 3; r1 >= 2; --r1) {
-        const int bm = 128 + 32 * r1;
-        const long t7 = (long)((a.M + bm - 1) / bm) * (a.N / GEMM7_BN);
-        if (t7 > 256) continue;                                          // one round only: beyond it the 256-row kernels' rate wins
-        const double e7 = fill((double)t7 / 256.0) * ((double)a.M / (((a.M + bm - 1) / bm) * (double)bm)) * GEMM7_RATE;
-        if (e7 > eb * 1.03) { best = r1; eb = e7; }
-    }
-    return best;
-}
-template <int ACT, bool F32, bool G, int R1, bool WEAVE = false>
-static void launch_gemm7(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    constexpr int bm = 128 + 32 * R1, lds = Gemm7Geo<R1>::LDS_BYTES;
-    a.tiles_m = (a.M + bm - 1) / bm;
-    a.tiles_n = a.N / GEMM7_BN;
-    lds_attr<gemm7_bf16_kernel<ACT, F32, G, R1, WEAVE>>(lds);
-    hipLaunchKernelGGL((gemm7_bf16_kernel<ACT, F32, G, R1, WEAVE>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds, s, a);
-}
-
-// Split-K factor for the 128x128 kernel (1 = do not split).  Only for grids that leave most resident slots empty: a lone
-// workgroup streams its K-tiles at ~0.64 us each (0.95 us when two share a CU), so a 96-tile grid with K = 4096 takes 42 us
-// however idle the chip is (scripts/kernel_bench.py --small).  Cost model in us per launch, d over the divisors of the
-// K-tile count: (K-tiles / d) x per-tile time at the resulting occupancy + partial write/reduce.
-static int choose_splitk(const GemmArgs& a, const GemmCtl& c) {
-    if (!c.ws || !c.splitk || (c.variant != 0 && c.variant != 1)) return 1;
-    const int tiles = a.tiles_m * a.tiles_n, nt = a.K / GEMM_BK;
-    if (tiles > SPLITK_MAX_TILES || nt < 32) return 1;       // measured: K = 1024 GEMMs lose (14.0 -> 19.7 us)
-    int best = 1;
-    double cb = 1e30;
-    for (int d = 1; d <= 32 && d * tiles <= SPLITK_MAX_WG; ++d) {
-        if (nt % d || nt / d < 4) continue;
-        const int wg = tiles * d;
-        const double per = wg <= 256 ? 0.64 : 0.95 * ((wg + 511) / 512);
-        const double cst = (nt / d) * per + (d > 1 ? 2.0 + 0.3 * d : 0.0);
-        if (cst < cb * (d > 1 ? 0.85 : 1.0)) { cb = cst; best = d; }
-    }
-    return best;
-}
-
-// Small-M form (64x64 tiles, gemm_s_bf16_kernel): when the 128x128 grid cannot even give every CU one tile, quartering the
-// tile spreads the operand stream over the idle CUs (a workgroup streams at ~55 GB/s whatever the chip does).  Same K order
-// as every other kernel -> same bits.  Measured crossover (scripts/kernel_bench.py --small): see profiles/.
-static bool want_small_m(const GemmArgs& a, const GemmCtl& c) {
-    if (c.variant == 32) return true;
-    if (c.variant != 0) return false;
-    return a.tiles_m * a.tiles_n <= 128 && a.K >= 512;   // measured crossover: wins at <= 128 tiles, loses at 152-160
-}
-
-// Epilogue form of the two ping-pong kernels (k_gemm.h gemm_store_tr): bf16 outputs WITHOUT a residual go through the
-// register-resident C^T epilogue (measured on MI355X, scripts/ubench/gemm_lab.hip: fc1 + QuickGELU 101.8 -> 95.6 us, gate/up
-// 393 -> 384 us, STC 1x1 convs -1.5..-4 %), outputs with a residual keep the LDS-transposing one (the residual's row-contiguous
-// 16-B loads, all requested up front, beat the 8-B pieces the C^T layout needs: 31.2 vs 35.8 us on the ViT out_proj).  Both forms
-// produce the same bits (hash-checked per shape), so the choice is invisible to every caller.
-static bool want_tr_epilogue(const GemmArgs& a) { return a.res == nullptr; }
-
-#ifdef VL2_LAB
-// gemm8 (k_gemm8.h): the 256 x 256 tile on four waves, one per SIMD, 128 x 128 wave tiles
-template <int ACT, bool SW, bool F32>
-static void launch_gemm8(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    a.tiles_m = (a.M + 255) / 256;
-    a.tiles_n = a.N / GEMM4_BN;
-    if constexpr (!F32) {
-        if (want_tr_epilogue(a)) {
-            lds_attr<gemm8_bf16_kernel<ACT, SW, false, true>>(GEMM8_LDS_BYTES);
-            hipLaunchKernelGGL((gemm8_bf16_kernel<ACT, SW, false, true>), dim3(a.tiles_m * a.tiles_n), dim3(256), GEMM8_LDS_BYTES, s, a);
-            return;
-        }
-    }
-    lds_attr<gemm8_bf16_kernel<ACT, SW, F32, false>>(GEMM8_LDS_BYTES);
-    hipLaunchKernelGGL((gemm8_bf16_kernel<ACT, SW, F32, false>), dim3(a.tiles_m * a.tiles_n), dim3(256), GEMM8_LDS_BYTES, s, a);
-}
-#endif
-
-// gemm9 (k_gemm9.h): the 256 x 256 ping-pong tile on the 16 x 16 x 32 matrix instruction -- opt-in, NOT the family's bits
-template <bool SW>
-static void launch_gemm9(const GemmArgs& a0, int mode, hipStream_t s) {
-    GemmArgs a = a0;
-    a.tiles_m = (a.M + 255) / 256;
-    a.tiles_n = a.N / GEMM4_BN;
-    const dim3 grid(a.tiles_m * a.tiles_n);
-    if (mode == 9) {          // variant 26: 64-deep phases, 5-stage ring = the whole 160 KiB of LDS
-        lds_attr<gemm9_bf16_kernel<SW, 9>>(5 * GEMM4_STAGE);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 9>), grid, dim3(512), 5 * GEMM4_STAGE, s, a);
-        return;
-    }
-    if constexpr (kLab) {
-    if (mode == 1) {          // lab (variant 17): the LDS-DMA issue behind the load phase's fragment reads
-        lds_attr<gemm9_bf16_kernel<SW, 1>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 1>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 2) {   // lab (variant 18): woven into the matrix phase
-        lds_attr<gemm9_bf16_kernel<SW, 2>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 2>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 7) {   // lab (variant 23): variant 16 with s_memtime stamps, sums into the workspace (scripts/gemm9_phase_stamps.py)
-        lds_attr<gemm9_bf16_kernel<SW, 7>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 7>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 8) {   // lab (variant 25): variant 16 with one stamp pair around the K loop
-        lds_attr<gemm9_bf16_kernel<SW, 8>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 8>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 4) {   // lab (variant 20): two pieces at the head of the load phase, two woven into the matrix phase
-        lds_attr<gemm9_bf16_kernel<SW, 4>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 4>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 5) {   // lab (variant 21): one / three
-        lds_attr<gemm9_bf16_kernel<SW, 5>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 5>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 6) {   // lab (variant 22): three / one
-        lds_attr<gemm9_bf16_kernel<SW, 6>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 6>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else if (mode == 3) {   // lab (variant 19): register-staged slabs (plain loads + ds_write_b128), no LDS-DMA
-        lds_attr<gemm9_bf16_kernel<SW, 3>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 3>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    }
-    if (mode != 0) return;
-    }
-    lds_attr<gemm9_bf16_kernel<SW, 0>>(GEMM4_LDS_BYTES);
-    hipLaunchKernelGGL((gemm9_bf16_kernel<SW, 0>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-}
-
-template <int ACT, bool SW, bool F32, int BM = GEMM4_BM>
-static void launch_gemm4(const GemmArgs& a0, hipStream_t s, bool weave4 = false) {
-    GemmArgs a = a0;
-    a.tiles_m = (a.M + BM - 1) / BM;
-    a.tiles_n = a.N / GEMM4_BN;
-    const dim3 grid(a.tiles_m * a.tiles_n);
-    // the product builds ONE issue order per tile height: woven (WEAVE4) on the 192-row tiles, load-phase on the 256-row tiles; the other
-    // order of each is a lab form (VL2_GEMM_NO_WEAVE4 / VL2_GEMM_WEAVE4)
-    constexpr bool kWoven = BM == 192 && !F32, kPlain = !kWoven;
-    if constexpr (!kLab) weave4 = kWoven;
-    if constexpr (BM == 160) {                       // one form: LDS epilogue, load-phase issue
-        lds_attr<gemm4_bf16_kernel<ACT, SW, F32, false, -1, 160>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm4_bf16_kernel<ACT, SW, F32, false, -1, 160>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else {
-    if constexpr (!F32) {
-        if (want_tr_epilogue(a)) {
-            if constexpr (kLab || kWoven) {
-                if (weave4) {
-                    lds_attr<gemm4_bf16_kernel<ACT, SW, false, true, -1, BM, true>>(GEMM4_LDS_BYTES);
-                    hipLaunchKernelGGL((gemm4_bf16_kernel<ACT, SW, false, true, -1, BM, true>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-                    return;
-                }
-            }
-            if constexpr (kLab || kPlain) {
-                lds_attr<gemm4_bf16_kernel<ACT, SW, false, true, -1, BM>>(GEMM4_LDS_BYTES);
-                hipLaunchKernelGGL((gemm4_bf16_kernel<ACT, SW, false, true, -1, BM>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-            }
-            return;
-        }
-        if constexpr (kLab || kWoven) {
-            if (weave4) {
-                lds_attr<gemm4_bf16_kernel<ACT, SW, false, false, -1, BM, true>>(GEMM4_LDS_BYTES);
-                hipLaunchKernelGGL((gemm4_bf16_kernel<ACT, SW, false, false, -1, BM, true>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-                return;
-            }
-        }
-    }
-    if constexpr (kLab || kPlain) {
-        lds_attr<gemm4_bf16_kernel<ACT, SW, F32, false, -1, BM>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm4_bf16_kernel<ACT, SW, F32, false, -1, BM>), grid, dim3(512), GEMM4_LDS_BYTES, s, a);
-    }
-    }
-}
-
-// ---- persistent ping-pong GEMM (k_gemm6.h): ONE workgroup per CU walks its tiles, the LDS ring runs across tile boundaries, the stores
-// of a tile are never waited for, the epilogue vectors arrive by LDS-DMA.  For bf16 outputs without residual / statistics / gather / remap
-// whose 256-row grid is more than one round of workgroups (a one-round grid has nothing to overlap).  Measured in the C++ lab on one box,
-// interleaved with the one-tile-per-workgroup kernels and bit-identical to them (profiles/r04_gemm_lab_persistent.txt): ViT q/k/v
-// 9232x3072x1024 65.8 -> 59.6 us, ViT fc1 + QuickGELU 94.5 -> 87.3 (101.8 -> 89.9 with the LayerNorm carried), STC K = 1024 conv
-// 81.8 -> 75.8, STC 4096x4096 conv 258.8 -> 254.0, 8192x4096x4096 216.2 -> 212.3 (1295 TF/s).
 static int cu_count() {
     static std::atomic<int> n{0};                                  // idempotent cache of a device constant (like lds_attr's bits)
     int v = n.load(std::memory_order_relaxed);
@@ -356,68 +123,6 @@ static int cu_count() {
         n.store(v, std::memory_order_relaxed);
     }
     return v;
-}
-static bool gemm6_ok(const GemmArgs& a, int bm) {
-    return a.res == nullptr && a.stats_out == nullptr && a.a_idx == nullptr && a.out_grp == 0 && a.res_row_mod == 0 &&
-           (a.norm == 0 || a.row_norm != nullptr) && a.N % GEMM4_BN == 0 && a.K % GEMM4_BK == 0 && a.K >= 1024 && a.M >= bm;
-}
-// 0 = not this call; 60 = 256-row tiles, 61 = 192-row tiles: the smaller makespan in units of a 256-row tile (a 192-row tile costs 0.75)
-static int choose_gemm6(const GemmArgs& a) {
-    // only with a counter block (dynamic tile hand-out): the static walk is as slow as its slowest CU (k_gemm6.h)
-    if (!gemm6_ok(a, 256) || a.tile_ctr == nullptr) return 0;
-    const int cus = cu_count();
-    const long t256 = (long)((a.M + 255) / 256) * (a.N / GEMM4_BN), t192 = (long)((a.M + 191) / 192) * (a.N / GEMM4_BN);
-    if (t256 <= cus) return 0;
-    const double ms256 = (double)((t256 + cus - 1) / cus), ms192 = 0.75 * (double)((t192 + cus - 1) / cus);
-    return ms192 < ms256 ? 71 : 70;
-}
-// kern: 60 / 61 / 62 static tile walk (256- / 192-row tiles / 192 rows + two accumulator sets), 70 / 71 = 60 / 61 through the counter block
-template <int ACT, bool SW>
-static void launch_gemm6(const GemmArgs& a0, int kern, hipStream_t s) {
-    GemmArgs a = a0;
-    a.tile_first_dyn = kern >= 80;                                     // 80 / 81: the first tile of a workgroup from the counter too
-    if (kern >= 80) kern -= 20; else if (kern >= 70) kern -= 10; else a.tile_ctr = nullptr;
-    const int bm = kern == 60 ? 256 : 192;
-    a.tiles_m = (a.M + bm - 1) / bm;
-    a.tiles_n = a.N / GEMM4_BN;
-    const long nt = (long)a.tiles_m * a.tiles_n;
-    const int g = (int)(nt < cu_count() ? nt : cu_count());
-    if (kern == 60) {
-        lds_attr<gemm6_bf16_kernel<ACT, SW, 256, false>>(GEMM6_LDS_BYTES);
-        hipLaunchKernelGGL((gemm6_bf16_kernel<ACT, SW, 256, false>), dim3(g), dim3(512), GEMM6_LDS_BYTES, s, a);
-    } else if (kern == 61) {
-        lds_attr<gemm6_bf16_kernel<ACT, SW, 192, false>>(GEMM6_LDS_BYTES);
-        hipLaunchKernelGGL((gemm6_bf16_kernel<ACT, SW, 192, false>), dim3(g), dim3(512), GEMM6_LDS_BYTES, s, a);
-    } else if constexpr (kLab) {                                       // 62: two accumulator sets (measured slower than 61)
-        lds_attr<gemm6_bf16_kernel<ACT, SW, 192, true>>(GEMM6_LDS_BYTES);
-        hipLaunchKernelGGL((gemm6_bf16_kernel<ACT, SW, 192, true>), dim3(g), dim3(512), GEMM6_LDS_BYTES, s, a);
-    }
-}
-
-// Row split (returns the number of leading rows that go to the 256x256 kernel, 0 = no split).  Two cases, both two launches on the
-// same stream; every kernel accumulates K in the same order and shares one epilogue, so the output bits do not change (asserted
-// in tests/test_gpu_ops.py):
-//  (1) M = 1621 leaves the 256-row kernel a 7th row tile with 85 live rows (9.5 % of its MFMA work wasted) and the 128-row kernel
-//      is slower per FLOP.  When N is wide enough for both parts to fill the chip, the first floor(M/256)*256 rows go to the
-//      256x256 kernel and the remaining rows to whatever the chooser picks for them.  Measured: 1621x28672x4096 + SwiGLU
-//      362 -> 345 us; loses on N <= 6144 and on M % 256 > 128.
-//  (2) whole rounds + a short tail: 9216x4096x4096 (the STC s1 convolutions) is 576 tiles = 2.25 rounds of 256 workgroups; the
-//      quarter round costs most of a full one.  The rows of the whole rounds stay on the 256x256 kernel, the tail rows (at most
-//      half a round of big tiles) go through the chooser, which gives them a finer-tiled one-round kernel
-//      (2 rounds 224 us + 1024 rows on the 8-wave 128x128 kernel ~40 us against 287 us for the single launch).
-static int m_split_rows(const GemmArgs& a, const GemmCtl& c) {
-    if (c.variant != 0 || a.out_grp > 0 || a.res_row_mod > 0 || a.N % GEMM4_BN || a.K < 1024 || a.M < 1024) return 0;
-    const int r = a.M % GEMM4_BM, m1_tiles = a.M / GEMM4_BM, n_tiles = a.N / GEMM4_BN;
-    if (r != 0 && r <= 96 && n_tiles >= 64) {
-        const long t4 = (long)m1_tiles * n_tiles;
-        if ((double)t4 / (double)(((t4 + 255) / 256) * 256) >= 0.85) return m1_tiles * GEMM4_BM;   // the 256-row part fills its rounds
-    }
-    if (256 % n_tiles == 0) {
-        const int per_round = 256 / n_tiles;                       // row tiles in one full round of 256 workgroups
-        const int mt = (a.M + GEMM4_BM - 1) / GEMM4_BM, rounds = mt / per_round, tail = mt - rounds * per_round;
-        if (rounds >= 1 && tail > 0 && tail * n_tiles <= 128) return rounds * per_round * GEMM4_BM;
-    }
-    return 0;
 }
 
 // rows [m0, m0 + rows) of a call as a call of its own (A / C / residual / statistics rows shifted; the gather table keeps its
@@ -436,309 +141,213 @@ static GemmArgs gemm_rows(const GemmArgs& a0, int m0, int rows, bool f32) {
     return a;
 }
 
+// One planned launch -> its instantiation.  ACT / SW / F32 / G are the call's epilogue and operand forms (gemm_dispatch); a `case` is compiled only
+// for the combinations its kernel is built for, and the lab forms only with -DVL2_LAB -- the plan never hands a form to a combination without it.
 template <int ACT, bool SW, bool F32, bool G>
-static void launch_gemm(const GemmArgs& a0, const GemmCtl& c, hipStream_t s) {
-    if constexpr (!G && !F32 && ACT == ACT_NONE) {
-        if (c.mfma16 && (c.variant == 23 || c.variant == 25)) {                         // the stamps need room for 8 waves x 6 u64 per workgroup
-            GemmArgs a = a0;
-            const long wgs = (long)((a.M + 255) / 256) * (a.N / 256);
-            a.sk_ws = (c.ws && c.ws_bytes >= wgs * 8 * 6 * 8) ? (float*)c.ws : nullptr;
-            launch_gemm9<SW>(a, c.variant == 23 ? 7 : 8, s);
-            return;
-        }
-        if (c.mfma16) {                                                                                                                         // (vl2_gemm has checked that the call qualifies)
-            // a row-split call keeps its ONE mixed launch (k_gemm9.h gemm_mix16_bf16_kernel): whole 256-row tiles on gemm9_body, the tail rows on the
-            // 128 x 128 body of the same instruction -- the same bits row by row, so the split stays invisible (as in the 32 x 32 x 16 family)
-            if (c.variant == 0 || c.variant == 16 || c.variant == 26 || (kLab && c.variant >= 27 && c.variant <= 29)) {
-                GemmCtl c0 = c;
-                c0.variant = 0;
-                if (const int M1 = m_split_rows(a0, c0); M1 > 0 && !c.no_mix) {
-                    GemmArgs big = gemm_rows(a0, 0, M1, false), tail = gemm_rows(a0, M1, a0.M - M1, false);
-                    if (kLab && c.variant >= 27) big.tile_group = c.variant == 27 ? 8 : c.variant == 28 ? 0 : 6;      // lab: variant 26 with another group depth
-                    if (kLab && c.variant == 28) tail.tile_group = -1;                                                // lab: variant 26 with the tail's empty waves computing (as before round 6's skip)
-                    const long t_big = (long)(M1 / GEMM4_BM) * (a0.N / GEMM4_BN), t_tail = (long)tail.tiles_m * tail.tiles_n;
-                    if (t_tail > 128 && t_tail <= 512) {
-                        big.tiles_m = M1 / GEMM4_BM; big.tiles_n = a0.N / GEMM4_BN;
-                        const dim3 gmix((unsigned)(t_big + t_tail));
-                        // the big tiles with 64-deep phases on the 5-stage ring (the whole 160 KiB of LDS): the flag's form and variant 26 (gate/up at
-                        // S = 945 / 1621 / 2973: 195.9 / 334.8 / 609.5 -> 192.4 / 332.2 / 596.9 us, profiles/r06_mix16_bench_64deep.txt); 16 = the 32-deep form
-                        // (SwiGLU calls only: without SwiGLU the tail body ends in gemm_rows_ticket, whose LDS word does not fit beside the 160-KiB ring)
-                        if constexpr (SW) {
-                            if (c.variant != 16) {
-                                lds_attr<gemm_mix16_bf16_kernel<SW, 9>>(5 * GEMM4_STAGE);
-                                hipLaunchKernelGGL((gemm_mix16_bf16_kernel<SW, 9>), gmix, dim3(512), 5 * GEMM4_STAGE, s, big, tail, (int)t_big);
-                                return;
-                            }
-                        }
-                        lds_attr<gemm_mix16_bf16_kernel<SW>>(GEMM4_LDS_BYTES);
-                        hipLaunchKernelGGL((gemm_mix16_bf16_kernel<SW>), gmix, dim3(512), GEMM4_LDS_BYTES, s, big, tail, (int)t_big);
-                        return;
-                    }
-                }
-            }
-            if constexpr (!SW) {
-                // the other two tiles of the 16 x 16 x 32 set (round 6: the decoder's o / down projections): at most one 128 x 128 tile per CU -> the one-round
-                // 128 x 128 body; a one-round grid of fill-the-round tiles where the family's rule picks them -> gemm7 on this instruction; else the 256 x 256 tile
-                if (c.variant == 0 || c.variant == 256 || c.variant == 224 || c.variant == 192) {       // (256 / 224 / 192 with the flag: that tile of the set on demand)
-                    if (c.variant == 256 || (c.variant == 0 && (long)a0.tiles_m * a0.tiles_n <= 256)) {
-                        lds_attr<gemm_l8_16_bf16_kernel<false>>(GEMML_LDS_BYTES);
-                        hipLaunchKernelGGL((gemm_l8_16_bf16_kernel<false>), dim3(a0.tiles_m * a0.tiles_n), dim3(512), GEMML_LDS_BYTES, s, a0);
-                        return;
-                    }
-                    // (lab: the fill-the-round tiles on this instruction, k_gemm7.h gemm7_loop16 -- bit-identical with the rest of the set, measured at parity
-                    //  with their 32 x 32 x 16 twins on the one-round grids they exist for: no call site uses them)
-                    if (const int r1 = !kLab ? 0 : c.variant == 224 ? 3 : c.variant == 192 ? 2 : c.no_fill ? 0 : choose_gemm7(a0, false); r1 != 0) {
-                        GemmArgs a = a0;
-                        const int bm = 128 + 32 * r1;
-                        a.tiles_m = (a.M + bm - 1) / bm;
-                        a.tiles_n = a.N / GEMM7_BN;
-#ifdef VL2_LAB
-                        if (r1 == 3) {
-                            lds_attr<gemm7_16_bf16_kernel<3>>(Gemm7Geo<3>::LDS_BYTES);
-                            hipLaunchKernelGGL((gemm7_16_bf16_kernel<3>), dim3(a.tiles_m * a.tiles_n), dim3(512), Gemm7Geo<3>::LDS_BYTES, s, a);
-                        } else {
-                            lds_attr<gemm7_16_bf16_kernel<2>>(Gemm7Geo<2>::LDS_BYTES);
-                            hipLaunchKernelGGL((gemm7_16_bf16_kernel<2>), dim3(a.tiles_m * a.tiles_n), dim3(512), Gemm7Geo<2>::LDS_BYTES, s, a);
-                        }
-                        return;
-#endif
-                    }
-                }
-            }
-            if (c.variant != 0 && c.variant != 16 && a0.row_norm_out && c.fin) *c.fin = true;      // only the shipped form (MODE 0) finalizes its rows itself
-            launch_gemm9<SW>(a0, c.variant >= 17 && c.variant <= 23 ? c.variant - 16 : c.variant == 26 ? 9 : 0, s);
-            return;
-        }
-    }
-    if constexpr (!SW) {
-        // fill-the-round tiles (k_gemm7.h): variants 224 / 192 on request (any shape with N % 128 == 0), or by the rule of choose_gemm7
-        const int r1 = c.variant == 224 ? 3 : c.variant == 192 ? 2 : (c.variant == 0 && !c.no_fill) ? choose_gemm7(a0, G) : 0;
-        // (225 / 193 = 224 / 192 with the LDS-DMA issue woven into the MFMA phases, as VL2_GEMM_WEAVE selects it: lab form, see gemm3 below)
-        const int r1v = c.variant == 225 ? 3 : c.variant == 193 ? 2 : r1;
-        const bool weave7 = kLab && (c.weave || c.variant == 225 || c.variant == 193);
-        if constexpr (kLab) {
-            if (weave7 && r1v == 3) { launch_gemm7<ACT, F32, G, 3, true>(a0, s); return; }
-            if (weave7 && r1v == 2) { launch_gemm7<ACT, F32, G, 2, true>(a0, s); return; }
-        }
-        if (r1v == 3) { launch_gemm7<ACT, F32, G, 3, false>(a0, s); return; }
-        if (r1v == 2) { launch_gemm7<ACT, F32, G, 2, false>(a0, s); return; }
-    }
-    if constexpr (!G && !F32) {
-        // persistent form: on request (variants 60 / 61; 62 = 192-row tiles with two accumulator sets, measured slower, kept for the lab) or
-        // by the rule of choose_gemm6; a forced variant the call does not qualify for falls through to the automatic choice below
-        const int v6 = c.variant;
-        const int k6 = v6 == 0 ? (c.persist && !c.no_persist ? choose_gemm6(a0) : 0)
-                     : (v6 == 60 || v6 == 61 || v6 == 62 || ((v6 == 70 || v6 == 71 || v6 == 80 || v6 == 81) && a0.tile_ctr)) &&
-                               gemm6_ok(a0, v6 == 60 || v6 == 70 || v6 == 80 ? 256 : 192) &&
-                               (v6 != 62 || a0.K >= 32 * 28) ? v6 : 0;
-        if (k6) { launch_gemm6<ACT, SW>(a0, k6, s); return; }
-        if (v6 == 24 || (v6 >= 60 && v6 <= 81)) {   // 24 = the automatic choice WITHOUT the persistent form (A/B)
-            GemmCtl c0 = c;
-            c0.variant = 0;
-            c0.no_persist = true;
-            launch_gemm<ACT, SW, F32, G>(a0, c0, s);
-            return;
-        }
-    }
-    if constexpr (!G && !F32) {
-        // (K < 2048 with an activation in the epilogue -- ViT fc1 + QuickGELU -- stays on its single launch: in the pipeline's rocprofv3 trace the
-        //  mixed form took 105 us against 98.6 for the 128x128 kernel, although it wins the isolated micro-benchmark; end to end the two are equal:
-        //  encode 12.52 vs 12.52 ms over three alternations)
-        if (const int M1 = (a0.K < 2048 && ACT != ACT_NONE) ? 0 : m_split_rows(a0, c); M1 > 0) {
-            GemmArgs big = gemm_rows(a0, 0, M1, F32), tail = gemm_rows(a0, M1, a0.M - M1, F32);
-            // ONE launch (k_gemm.h gemm_mix_bf16_kernel) when the tail is 129..512 tiles of the 8-wave 128x128 body: its workgroups start on
-            // the CUs that run out of big tiles instead of behind a second launch.  Measured against the two launches on one box
-            // (scripts/gpu_r3_k.sh): gate/up at S = 1621 383.0 -> 369.7 us (prefill 26.0 -> 25.6 ms), STC 4096x4096 conv 274.7 -> 265.0,
-            // STC K = 1024 conv 85.9 -> 82.2, ViT fc1 99.2 -> 96.5 (T = 8: 54.7 -> 49.9); in the pipeline the K = 1024 cases are neutral at T = 16
-            // (encode 12.90 vs 12.89 ms) and the prefill gains 0.4 ms.  VL2_GEMM_NO_MIX in the descriptor keeps two launches / the single kernel.
-            const bool no_mix = c.no_mix;
-            const long t_big = (long)(M1 / GEMM4_BM) * (a0.N / GEMM4_BN), t_tail = (long)tail.tiles_m * tail.tiles_n;
-            if (!no_mix && t_tail > 128 && t_tail <= 512) {
-                big.tiles_m = M1 / GEMM4_BM; big.tiles_n = a0.N / GEMM4_BN;
-                const dim3 gmix((unsigned)(t_big + t_tail));
-                if constexpr (kLab) {                 // the big tiles with the woven LDS-DMA issue (VL2_GEMM_WEAVE4)
-                    if (c.weave4) {
-                        if (want_tr_epilogue(big)) {
-                            lds_attr<gemm_mix_bf16_kernel<ACT, SW, true, true>>(GEMM4_LDS_BYTES);
-                            hipLaunchKernelGGL((gemm_mix_bf16_kernel<ACT, SW, true, true>), gmix, dim3(512), GEMM4_LDS_BYTES, s, big, tail, (int)t_big);
-                        } else {
-                            lds_attr<gemm_mix_bf16_kernel<ACT, SW, false, true>>(GEMM4_LDS_BYTES);
-                            hipLaunchKernelGGL((gemm_mix_bf16_kernel<ACT, SW, false, true>), gmix, dim3(512), GEMM4_LDS_BYTES, s, big, tail, (int)t_big);
-                        }
-                        return;
-                    }
-                }
-                if (want_tr_epilogue(big)) {
-                    lds_attr<gemm_mix_bf16_kernel<ACT, SW, true>>(GEMM4_LDS_BYTES);
-                    hipLaunchKernelGGL((gemm_mix_bf16_kernel<ACT, SW, true>), gmix, dim3(512), GEMM4_LDS_BYTES, s, big, tail, (int)t_big);
-                } else {
-                    lds_attr<gemm_mix_bf16_kernel<ACT, SW, false>>(GEMM4_LDS_BYTES);
-                    hipLaunchKernelGGL((gemm_mix_bf16_kernel<ACT, SW, false>), gmix, dim3(512), GEMM4_LDS_BYTES, s, big, tail, (int)t_big);
-                }
-                return;
-            }
-            if (a0.K >= 2048) {                       // two launches (measured wins at K >= 2048 only: profiles/r02_experiments.md section 3)
-                launch_gemm4<ACT, SW, F32>(big, s, c.weave4);
-                launch_gemm<ACT, SW, F32, G>(tail, c, s);
-                return;
-            }
-        }
-    }
-    if constexpr (!SW && !F32) {
-        if (choose_splitk(a0, c) <= 1 && want_small_m(a0, c)) {
-            if (a0.row_norm_out && c.fin) *c.fin = true;
-            lds_attr<gemm_s_bf16_kernel<ACT, G>>(GEMMS_LDS_BYTES);
-            GemmArgs a = a0;
-            a.tiles_m = (a.M + GEMMS_BM - 1) / GEMMS_BM;
-            a.tiles_n = a.N / GEMMS_BN;
-            hipLaunchKernelGGL((gemm_s_bf16_kernel<ACT, G>), dim3(a.tiles_m * a.tiles_n), dim3(128), GEMMS_LDS_BYTES, s, a);
-            return;
-        }
-    }
-    if (const int split = choose_splitk(a0, c); split > 1) {
-        if (a0.row_norm_out && c.fin) *c.fin = true;
-        lds_attr<gemm_bf16_kernel<ACT, SW, F32, G, false, true>>(GEMM_LDS_BYTES);
-        GemmArgs a = a0;
-        a.sk_ws = (float*)c.ws;
-        a.sk_flags = (int*)((char*)c.ws + SPLITK_CNT_OFF);
-        hipLaunchKernelGGL((gemm_bf16_kernel<ACT, SW, F32, G, false, true>), dim3(a.tiles_m * a.tiles_n, split), dim3(256), GEMM_LDS_BYTES, s, a);
+static void launch_planned(const GemmArgs& a0, const GemmLaunch& l, void* ws, hipStream_t s) {
+    GemmArgs a = gemm_rows(a0, l.m0, l.rows, F32);
+    a.tiles_m = l.tiles_m;
+    a.tiles_n = l.tiles_n;
+    a.tile_group = l.tile_group;
+    const dim3 grid(l.grid_x, l.grid_y), b128(128), b256(256), b512(512);
+    constexpr bool kPlain = !G && !F32 && ACT == ACT_NONE;      // what the 16 x 16 x 32 kernels are built for
+    switch (l.form) {
+    case GF_128:
+        launch<gemm_bf16_kernel<ACT, SW, F32, G>>(grid, b256, GEMM_LDS_BYTES, s, a);   // 64 KiB dynamic LDS needs the opt-in once per kernel instance
         return;
-    }
-    if constexpr (!G) {
-        // measured (scripts/kernel_bench.py --frames 8): wins 15-20 % at <= 256 tiles with K >= 4096, loses at K = 1024 and beyond one round
-        if (c.variant == 256 || (c.variant == 0 && (long)a0.tiles_m * a0.tiles_n <= 256 && a0.K >= 4096)) {
-            lds_attr<gemm_l8_bf16_kernel<ACT, SW, F32>>(GEMML_LDS_BYTES);
-            hipLaunchKernelGGL((gemm_l8_bf16_kernel<ACT, SW, F32>), dim3(a0.tiles_m * a0.tiles_n), dim3(512), GEMML_LDS_BYTES, s, a0);
-            return;
+    case GF_128_SPLITK:
+        a.sk_ws = (float*)ws;
+        a.sk_flags = (int*)((char*)ws + SPLITK_CNT_OFF);
+        launch<gemm_bf16_kernel<ACT, SW, F32, G, false, true>>(grid, b256, GEMM_LDS_BYTES, s, a);
+        return;
+    case GF_128_STREAMK:
+        if constexpr (!G && kLab) {
+            a.sk_ws = (float*)ws;
+            a.sk_flags = (int*)((char*)ws + SK_FLAGS_OFF);
+            a.sk_per = (a.tiles_m * a.tiles_n * (a.K / GEMM_BK) + SK_GRID - 1) / SK_GRID;
+            lds_attr<gemm_sk_bf16_kernel<ACT, SW, F32>>(GEMM_LDS_BYTES);
+            check(hipMemsetAsync(a.sk_flags, 0, (SK_GRID + 1) * 4, s));               // flags re-armed before EVERY launch (guide G16)
+            hipLaunchKernelGGL((gemm_sk_bf16_kernel<ACT, SW, F32>), grid, b256, GEMM_LDS_BYTES, s, a);
         }
-        const int kern = c.variant == 0 ? choose_gemm_kernel(a0) : c.variant;
-        if ((kern == 4 || kern == 5) && a0.N % GEMM3_BN == 0) {
-            // WEAVE (k_gemm.h gemm3_body; same bits): the LDS-DMA issue woven into the MFMA phases.  Measured round 5 (profiles/r05_experiments.md):
-            // -2...-9 % back to back with the operands warm in the Infinity Cache, but +4...+12 % IN THE PIPELINE (down 206 -> 218 us, o 66 -> 69,
-            // Conv3d on the 192-row tiles 425 -> 476): the woven pieces have 1.5 phases of flight instead of 3, which cold weights do not forgive.
-            // So it is a lab switch: variant 5 or VL2_GEMM_WEAVE.
-            const bool weave = kLab && (kern == 5 || c.weave);
-            GemmArgs a = a0;
-            a.tiles_m = (a.M + GEMM3_BM - 1) / GEMM3_BM;
-            a.tiles_n = a.N / GEMM3_BN;
-            const dim3 grid(a.tiles_m * a.tiles_n);
+        return;
+    case GF_64:
+        if constexpr (!SW && !F32) launch<gemm_s_bf16_kernel<ACT, G>>(grid, b128, GEMMS_LDS_BYTES, s, a);
+        return;
+    case GF_L8:
+        if constexpr (!G) launch<gemm_l8_bf16_kernel<ACT, SW, F32>>(grid, b512, GEMML_LDS_BYTES, s, a);
+        return;
+    case GF_128x256:
+        if constexpr (!G) {
             if constexpr (kLab) {
-                if (weave) {
+                if (l.woven) {
                     if constexpr (!F32) {
-                        if (want_tr_epilogue(a)) {
-                            lds_attr<gemm3_bf16_kernel<ACT, SW, false, true, -1, true>>(GEMM3_LDS_BYTES);
-                            hipLaunchKernelGGL((gemm3_bf16_kernel<ACT, SW, false, true, -1, true>), grid, dim3(512), GEMM3_LDS_BYTES, s, a);
-                            return;
-                        }
+                        if (l.tr) { launch<gemm3_bf16_kernel<ACT, SW, false, true, -1, true>>(grid, b512, GEMM3_LDS_BYTES, s, a); return; }
                     }
-                    lds_attr<gemm3_bf16_kernel<ACT, SW, F32, false, -1, true>>(GEMM3_LDS_BYTES);
-                    hipLaunchKernelGGL((gemm3_bf16_kernel<ACT, SW, F32, false, -1, true>), grid, dim3(512), GEMM3_LDS_BYTES, s, a);
+                    launch<gemm3_bf16_kernel<ACT, SW, F32, false, -1, true>>(grid, b512, GEMM3_LDS_BYTES, s, a);
                     return;
                 }
             }
             if constexpr (!F32) {
-                if (want_tr_epilogue(a)) {
-                    lds_attr<gemm3_bf16_kernel<ACT, SW, false, true>>(GEMM3_LDS_BYTES);
-                    hipLaunchKernelGGL((gemm3_bf16_kernel<ACT, SW, false, true>), grid, dim3(512), GEMM3_LDS_BYTES, s, a);
+                if (l.tr) { launch<gemm3_bf16_kernel<ACT, SW, false, true>>(grid, b512, GEMM3_LDS_BYTES, s, a); return; }
+            }
+            launch<gemm3_bf16_kernel<ACT, SW, F32>>(grid, b512, GEMM3_LDS_BYTES, s, a);
+        }
+        return;
+    case GF_G4_256:           // the product builds the load-phase issue only (the woven one: lab)
+        if constexpr (!G) {
+            if constexpr (!F32) {
+                if constexpr (kLab) {
+                    if (l.woven) {
+                        if (l.tr) launch<gemm4_bf16_kernel<ACT, SW, false, true, -1, 256, true>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+                        else launch<gemm4_bf16_kernel<ACT, SW, false, false, -1, 256, true>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+                        return;
+                    }
+                }
+                if (l.tr) { launch<gemm4_bf16_kernel<ACT, SW, false, true, -1, 256>>(grid, b512, GEMM4_LDS_BYTES, s, a); return; }
+            }
+            launch<gemm4_bf16_kernel<ACT, SW, F32, false, -1, 256>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+        }
+        return;
+    case GF_G4_192:           // bf16 outputs only; the product builds the woven issue only (the load-phase one: lab)
+        if constexpr (!G && !F32) {
+            if constexpr (kLab) {
+                if (!l.woven) {
+                    if (l.tr) launch<gemm4_bf16_kernel<ACT, SW, false, true, -1, 192>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+                    else launch<gemm4_bf16_kernel<ACT, SW, false, false, -1, 192>>(grid, b512, GEMM4_LDS_BYTES, s, a);
                     return;
                 }
             }
-            lds_attr<gemm3_bf16_kernel<ACT, SW, F32>>(GEMM3_LDS_BYTES);
-            hipLaunchKernelGGL((gemm3_bf16_kernel<ACT, SW, F32>), grid, dim3(512), GEMM3_LDS_BYTES, s, a);
-            return;
+            if (l.tr) launch<gemm4_bf16_kernel<ACT, SW, false, true, -1, 192, true>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+            else launch<gemm4_bf16_kernel<ACT, SW, false, false, -1, 192, true>>(grid, b512, GEMM4_LDS_BYTES, s, a);
         }
+        return;
+    case GF_G4_160:
+        if constexpr (!G && !F32 && !SW && kLab) launch<gemm4_bf16_kernel<ACT, SW, false, false, -1, 160>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+        return;
+    case GF_GEMM6:
+        if constexpr (!G && !F32) {
+            a.tile_first_dyn = l.dyn == 2;
+            if (l.dyn == 0) a.tile_ctr = nullptr;
+            if (l.tile_h == 256) launch<gemm6_bf16_kernel<ACT, SW, 256, false>>(grid, b512, GEMM6_LDS_BYTES, s, a);
+            else if (!l.acc2) launch<gemm6_bf16_kernel<ACT, SW, 192, false>>(grid, b512, GEMM6_LDS_BYTES, s, a);
+            else if constexpr (kLab) launch<gemm6_bf16_kernel<ACT, SW, 192, true>>(grid, b512, GEMM6_LDS_BYTES, s, a);      // measured slower than one set
+        }
+        return;
+    case GF_GEMM7:
+        if constexpr (!SW) {
+            if constexpr (kLab) {
+                if (l.woven && l.tile_h == 224) { launch<gemm7_bf16_kernel<ACT, F32, G, 3, true>>(grid, b512, Gemm7Geo<3>::LDS_BYTES, s, a); return; }
+                if (l.woven) { launch<gemm7_bf16_kernel<ACT, F32, G, 2, true>>(grid, b512, Gemm7Geo<2>::LDS_BYTES, s, a); return; }
+            }
+            if (l.tile_h == 224) launch<gemm7_bf16_kernel<ACT, F32, G, 3, false>>(grid, b512, Gemm7Geo<3>::LDS_BYTES, s, a);
+            else launch<gemm7_bf16_kernel<ACT, F32, G, 2, false>>(grid, b512, Gemm7Geo<2>::LDS_BYTES, s, a);
+        }
+        return;
 #ifdef VL2_LAB
-        if (kern == 9 && a0.N % GEMM4_BN == 0) {                              // lab / forced: the four-wave 256 x 256 kernel (k_gemm8.h)
-            launch_gemm8<ACT, SW, F32>(a0, s);
-            return;
+    case GF_GEMM8:
+        if constexpr (!G) {
+            if constexpr (!F32) {
+                if (l.tr) { launch<gemm8_bf16_kernel<ACT, SW, false, true>>(grid, b256, GEMM8_LDS_BYTES, s, a); return; }
+            }
+            launch<gemm8_bf16_kernel<ACT, SW, F32, false>>(grid, b256, GEMM8_LDS_BYTES, s, a);
         }
+        return;
+    case GF_GEMM7_16:
+        if constexpr (kPlain && !SW) {
+            if (l.tile_h == 224) launch<gemm7_16_bf16_kernel<3>>(grid, b512, Gemm7Geo<3>::LDS_BYTES, s, a);
+            else launch<gemm7_16_bf16_kernel<2>>(grid, b512, Gemm7Geo<2>::LDS_BYTES, s, a);
+        }
+        return;
 #endif
-        if ((kern == 8 || (F32 && kern == 12)) && a0.N % GEMM4_BN == 0) {     // (the 192-row form is built for bf16 outputs only)
-            launch_gemm4<ACT, SW, F32>(a0, s, c.weave4);
-            return;
+    case GF_GEMM9:            // MODE 9 (variant 26): 64-deep phases, 5-stage ring = the whole 160 KiB of LDS; MODE 1 ... 8: lab (variants 17 ... 23, 25; k_gemm9.h)
+        if constexpr (kPlain) {
+            if (l.mode == 7 || l.mode == 8) a.sk_ws = l.ws_wired ? (float*)ws : nullptr;      // the stamps' sums go into the workspace (scripts/gemm9_phase_stamps.py)
+            if (l.mode == 9) { launch<gemm9_bf16_kernel<SW, 9>>(grid, b512, 5 * GEMM4_STAGE, s, a); return; }
+            if constexpr (kLab) {
+                switch (l.mode) {
+                case 1: launch<gemm9_bf16_kernel<SW, 1>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 2: launch<gemm9_bf16_kernel<SW, 2>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 3: launch<gemm9_bf16_kernel<SW, 3>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 4: launch<gemm9_bf16_kernel<SW, 4>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 5: launch<gemm9_bf16_kernel<SW, 5>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 6: launch<gemm9_bf16_kernel<SW, 6>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 7: launch<gemm9_bf16_kernel<SW, 7>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                case 8: launch<gemm9_bf16_kernel<SW, 8>>(grid, b512, GEMM4_LDS_BYTES, s, a); return;
+                }
+            }
+            launch<gemm9_bf16_kernel<SW, 0>>(grid, b512, GEMM4_LDS_BYTES, s, a);
         }
-        if constexpr (!F32 && !SW && kLab) {
-            if (kern == 10 && a0.N % GEMM4_BN == 0) {                          // lab: 160-row tiles (measured: not faster than the 192-row tiles)
-                launch_gemm4<ACT, SW, false, 160>(a0, s);
+        return;
+    case GF_L8_16:
+        if constexpr (kPlain && !SW) launch<gemm_l8_16_bf16_kernel<false>>(grid, b512, GEMML_LDS_BYTES, s, a);
+        return;
+    case GF_MIX:
+    case GF_MIX16:
+        if constexpr (!G && !F32) {
+            GemmArgs tail = gemm_rows(a0, l.m0 + l.rows, l.tail_rows, F32);
+            tail.tiles_m = l.tail_tiles_m;
+            tail.tiles_n = l.tail_tiles_n;
+            tail.tile_group = l.tail_tile_group;
+            const int n_big = l.tiles_m * l.tiles_n;
+            if (l.form == GF_MIX16) {
+                if constexpr (kPlain) {
+                    if constexpr (SW) {
+                        if (l.mode == 9) { launch<gemm_mix16_bf16_kernel<SW, 9>>(grid, b512, 5 * GEMM4_STAGE, s, a, tail, n_big); return; }
+                    }
+                    launch<gemm_mix16_bf16_kernel<SW>>(grid, b512, GEMM4_LDS_BYTES, s, a, tail, n_big);
+                }
                 return;
             }
-        }
-        if constexpr (!F32) {
-            if (kern == 12 && a0.N % GEMM4_BN == 0) {
-                // 192-row tiles take the woven LDS-DMA issue by default (round 5, scripts/weave4_bench.py, interleaved on one box, same bits): their load
-                // phase carries 3-4 pieces + 10 fragment reads under a partner's TWELVE MFMAs -- ViT fc2 82.5 -> 79.4 us, out_proj 30.1 -> 29.3, the
-                // decoder's q/k/v 82.0 -> 81.6; the 256-row bodies measure the same either way (16 MFMAs cover the load phase) and keep the load-phase issue
-                launch_gemm4<ACT, SW, false, 192>(a0, s, !c.no_weave4);
-                return;
+            if constexpr (kLab) {
+                if (l.woven) {
+                    if (l.tr) launch<gemm_mix_bf16_kernel<ACT, SW, true, true>>(grid, b512, GEMM4_LDS_BYTES, s, a, tail, n_big);
+                    else launch<gemm_mix_bf16_kernel<ACT, SW, false, true>>(grid, b512, GEMM4_LDS_BYTES, s, a, tail, n_big);
+                    return;
+                }
             }
+            if (l.tr) launch<gemm_mix_bf16_kernel<ACT, SW, true>>(grid, b512, GEMM4_LDS_BYTES, s, a, tail, n_big);
+            else launch<gemm_mix_bf16_kernel<ACT, SW, false>>(grid, b512, GEMM4_LDS_BYTES, s, a, tail, n_big);
         }
+        return;
     }
-    if constexpr (!G && kLab) {
-        if (want_stream_k(a0, c)) {
-            lds_attr<gemm_sk_bf16_kernel<ACT, SW, F32>>(GEMM_LDS_BYTES);
-            GemmArgs a = a0;
-            const int total = a.tiles_m * a.tiles_n * (a.K / GEMM_BK);
-            a.sk_ws = (float*)c.ws;
-            a.sk_flags = (int*)((char*)c.ws + SK_FLAGS_OFF);
-            a.sk_per = (total + SK_GRID - 1) / SK_GRID;
-            check(hipMemsetAsync(a.sk_flags, 0, (SK_GRID + 1) * 4, s));               // flags re-armed before EVERY launch (guide G16)
-            hipLaunchKernelGGL((gemm_sk_bf16_kernel<ACT, SW, F32>), dim3(SK_GRID), dim3(256), GEMM_LDS_BYTES, s, a);
-            return;
-        }
-    }
-    lds_attr<gemm_bf16_kernel<ACT, SW, F32, G>>(GEMM_LDS_BYTES);   // 64 KiB dynamic LDS needs the opt-in once per kernel instance
-    hipLaunchKernelGGL((gemm_bf16_kernel<ACT, SW, F32, G>), dim3(a0.tiles_m * a0.tiles_n), dim3(256), GEMM_LDS_BYTES, s, a0);
 }
 
-// ---- fp8 form (VL2_GEMM_FP8): A and W are e4m3fn bytes; the kernels see a row of K bytes as K / 2 16-bit "elements" (k_gemm.h gemm3 / gemm4 FP8),
-// so `a` arrives with K, lda, ldw already halved.  128 x 256, 256 x 256 or 192 x 256 ping-pong tiles by the efficiency model of the 16-bit choice
-// (the 128 x 128 kernels are not built for fp8), LDS epilogue with the row table and the column scales.
+// the fp8 form's three kernels (`a` arrives with K, lda, ldw already halved: the kernels see a row of K bytes as K / 2 16-bit "elements")
 template <int ACT, bool SW, bool F32>
-static int32_t launch_gemm_fp8(const GemmArgs& a0, int variant, hipStream_t s) {
+static void launch_planned_fp8(const GemmArgs& a0, const GemmLaunch& l, hipStream_t s) {
     GemmArgs a = a0;
-    int kern = variant ? variant : choose_gemm_kernel(a);
-    if (kern != 4 && kern != 8 && kern != 12) kern = 4;
-    if (F32 && kern == 12) kern = 8;
-    a.tiles_n = a.N / 256;
-    if (kern == 4) {
-        a.tiles_m = (a.M + GEMM3_BM - 1) / GEMM3_BM;
-        lds_attr<gemm3_fp8_kernel<ACT, SW, F32>>(GEMM3_LDS_BYTES);
-        hipLaunchKernelGGL((gemm3_fp8_kernel<ACT, SW, F32>), dim3(a.tiles_m * a.tiles_n), dim3(512), GEMM3_LDS_BYTES, s, a);
-    } else if (kern == 8) {
-        a.tiles_m = (a.M + 255) / 256;
-        lds_attr<gemm4_fp8_kernel<ACT, SW, F32, 256>>(GEMM4_LDS_BYTES);
-        hipLaunchKernelGGL((gemm4_fp8_kernel<ACT, SW, F32, 256>), dim3(a.tiles_m * a.tiles_n), dim3(512), GEMM4_LDS_BYTES, s, a);
-    } else {
-        if constexpr (!F32) {
-            a.tiles_m = (a.M + 191) / 192;
-            lds_attr<gemm4_fp8_kernel<ACT, SW, false, 192>>(GEMM4_LDS_BYTES);
-            hipLaunchKernelGGL((gemm4_fp8_kernel<ACT, SW, false, 192>), dim3(a.tiles_m * a.tiles_n), dim3(512), GEMM4_LDS_BYTES, s, a);
-        }
-    }
-    return 0;
+    a.tiles_m = l.tiles_m;
+    a.tiles_n = l.tiles_n;
+    const dim3 grid(l.grid_x), b512(512);
+    if (l.form == GF_FP8_128x256) launch<gemm3_fp8_kernel<ACT, SW, F32>>(grid, b512, GEMM3_LDS_BYTES, s, a);
+    else if (l.form == GF_FP8_256) launch<gemm4_fp8_kernel<ACT, SW, F32, 256>>(grid, b512, GEMM4_LDS_BYTES, s, a);
+    else if constexpr (!F32) launch<gemm4_fp8_kernel<ACT, SW, false, 192>>(grid, b512, GEMM4_LDS_BYTES, s, a);
 }
 
-// one chunk (every operand within the kernels' 32-bit buffer offsets) -> the right instantiation
-static int32_t gemm_dispatch(const GemmArgs& a, const GemmCtl& c, int act, bool sw, bool f32, hipStream_t s) {
-    const bool g = a.a_idx != nullptr;
-    if (a.out_grp > 0 || a.res_row_mod > 0) {                      // row-remap epilogue (patch-embed): dedicated instantiation
-        lds_attr<gemm_bf16_kernel<ACT_NONE, false, false, false, true>>(GEMM_LDS_BYTES);
-        hipLaunchKernelGGL((gemm_bf16_kernel<ACT_NONE, false, false, false, true>), dim3(a.tiles_m * a.tiles_n), dim3(256), GEMM_LDS_BYTES, s, a);
-        return 0;
-    }
-    if (sw) launch_gemm<ACT_NONE, true, false, false>(a, c, s);
-    else if (g) {
-        if (act == VL2_ACT_SILU) launch_gemm<ACT_SILU, false, false, true>(a, c, s);
-        else launch_gemm<ACT_NONE, false, false, true>(a, c, s);
-    } else if (f32) launch_gemm<ACT_NONE, false, true, false>(a, c, s);
-    else {
-        switch (act) {
-            case VL2_ACT_NONE: launch_gemm<ACT_NONE, false, false, false>(a, c, s); break;
-            case VL2_ACT_QGELU: launch_gemm<ACT_QGELU, false, false, false>(a, c, s); break;
-            case VL2_ACT_GELU: launch_gemm<ACT_GELU, false, false, false>(a, c, s); break;
-            case VL2_ACT_SILU: launch_gemm<ACT_SILU, false, false, false>(a, c, s); break;
-            case VL2_ACT_GELU_TANH: launch_gemm<ACT_GELU_TANH, false, false, false>(a, c, s); break;
-            default: return fail(VL2_E_UNSUPP, "vl2_gemm: unknown act %d", act);
+// one chunk (every operand within the kernels' 32-bit buffer offsets): its plan, launch by launch, on the right instantiation.  *need_fin is set
+// when a planned kernel leaves `row_norm_out` to a row_norm_finalize launch.
+static int32_t gemm_dispatch(const GemmArgs& a, GemmPlanIn in, int act, void* ws, bool* need_fin, hipStream_t s) {
+    in.M = a.M; in.N = a.N;
+    in.row_norm_out = a.row_norm_out != nullptr;
+    const GemmPlan p = gemm_plan(in);
+    for (int i = 0; i < p.n; ++i) {
+        const GemmLaunch& l = p.l[i];
+        if (l.needs_finalize) *need_fin = true;
+        if (l.form == GF_REMAP) launch<gemm_bf16_kernel<ACT_NONE, false, false, false, true>>(dim3(l.grid_x), dim3(256), GEMM_LDS_BYTES, s, a);
+        else if (in.swiglu) launch_planned<ACT_NONE, true, false, false>(a, l, ws, s);
+        else if (in.gather) {
+            if (act == VL2_ACT_SILU) launch_planned<ACT_SILU, false, false, true>(a, l, ws, s);
+            else launch_planned<ACT_NONE, false, false, true>(a, l, ws, s);
+        } else if (in.f32) launch_planned<ACT_NONE, false, true, false>(a, l, ws, s);
+        else {
+            switch (act) {
+                case VL2_ACT_NONE: launch_planned<ACT_NONE, false, false, false>(a, l, ws, s); break;
+                case VL2_ACT_QGELU: launch_planned<ACT_QGELU, false, false, false>(a, l, ws, s); break;
+                case VL2_ACT_GELU: launch_planned<ACT_GELU, false, false, false>(a, l, ws, s); break;
+                case VL2_ACT_SILU: launch_planned<ACT_SILU, false, false, false>(a, l, ws, s); break;
+                case VL2_ACT_GELU_TANH: launch_planned<ACT_GELU_TANH, false, false, false>(a, l, ws, s); break;
+                default: return fail(VL2_E_UNSUPP, "vl2_gemm: unknown act %d", act);
+            }
         }
     }
     return 0;
@@ -773,10 +382,13 @@ extern "C" int32_t vl2_gemm(const vl2_gemm_desc* d, void* stream) {
         a.norm = VL2_NORM_RMS; a.row_norm = d->row_norm; a.col_scale = d->col_scale;
         a.stats_out_np = N / 64; a.stats_in_np = a.K / 64; a.idx_ld = M;
         hipStream_t s8 = ST(stream);
-        if (sw) launch_gemm_fp8<ACT_NONE, true, false>(a, v8, s8);
-        else if (f32) launch_gemm_fp8<ACT_NONE, false, true>(a, v8, s8);
-        else if (act == VL2_ACT_NONE) launch_gemm_fp8<ACT_NONE, false, false>(a, v8, s8);
-        else if (act == VL2_ACT_SILU) launch_gemm_fp8<ACT_SILU, false, false>(a, v8, s8);
+        GemmPlanIn in8{};
+        in8.M = M; in8.N = N; in8.K = K; in8.f32 = f32; in8.fp8 = true; in8.variant = v8;
+        const GemmLaunch l8 = gemm_plan(in8).l[0];
+        if (sw) launch_planned_fp8<ACT_NONE, true, false>(a, l8, s8);
+        else if (f32) launch_planned_fp8<ACT_NONE, false, true>(a, l8, s8);
+        else if (act == VL2_ACT_NONE) launch_planned_fp8<ACT_NONE, false, false>(a, l8, s8);
+        else if (act == VL2_ACT_SILU) launch_planned_fp8<ACT_SILU, false, false>(a, l8, s8);
         else return fail(VL2_E_UNSUPP, "vl2_gemm: the fp8 form supports act none / silu");
         return launched("vl2_gemm (fp8)");
     }
@@ -805,21 +417,24 @@ extern "C" int32_t vl2_gemm(const vl2_gemm_desc* d, void* stream) {
     if (!(v == 0 || v == 1 || v == 2 || v == 4 || v == 5 || v == 8 || v == 9 || v == 10 || v == 12 || (v >= 16 && v <= 23) || v == 25 || (v >= 26 && v <= 29) || v == 32 || v == 24 || v == 60 || v == 61 || v == 62 || v == 70 || v == 71 || v == 80 || v == 81 || v == 192 || v == 193 || v == 224 || v == 225 || v == 256)) return fail(VL2_E_BADARG, "vl2_gemm: unknown variant %d", v);
     if (!kLab && (v == 2 || v == 5 || v == 9 || v == 10 || (v >= 17 && v <= 23) || v == 25 || (v >= 27 && v <= 29) || v == 62 || v == 193 || v == 225))
         return fail(VL2_E_UNSUPP, "vl2_gemm: variant %d is a lab form: built into libvl2hip_lab.so only (scripts/build_lab_lib.sh)", v);
-    GemmCtl ctl{d->ws, d->ws_bytes, v, (d->flags & VL2_GEMM_SPLITK) != 0};
-    ctl.persist = (d->flags & VL2_GEMM_PERSISTENT) != 0;
-    ctl.no_mix = (d->flags & VL2_GEMM_NO_MIX) != 0;
-    ctl.no_fill = (d->flags & VL2_GEMM_NO_FILL) != 0;
-    ctl.weave = (d->flags & VL2_GEMM_WEAVE) != 0;
-    ctl.weave4 = (d->flags & VL2_GEMM_WEAVE4) != 0;
-    ctl.no_weave4 = (d->flags & VL2_GEMM_NO_WEAVE4) != 0;
-    {   // the 16 x 16 x 32 kernel: plain rows, bf16 output, no activation, no statistics out; the flag is a wish (ignored where the kernel is not built), variant 16 a demand
-        const bool ok16 = !g && !f32 && !remap && act == VL2_ACT_NONE && N % 256 == 0 && !(d->stats_out && (d->flags & VL2_GEMM_SWIGLU));
-        if (((v >= 16 && v <= 23) || (v >= 25 && v <= 29)) && !ok16) return fail(VL2_E_UNSUPP, "vl2_gemm: variant 16 (16x16x32 MFMA) is built for plain bf16 outputs without activation / gather / remap / stats_out, N %% 256 == 0");
-        ctl.mfma16 = ok16 && ((v >= 16 && v <= 23) || (v >= 25 && v <= 29) ||
-                              ((v == 0 || ((v == 256 || v == 224 || v == 192) && !(d->flags & VL2_GEMM_SWIGLU))) && (d->flags & VL2_GEMM_MFMA16)));     // 17 ... 22: lab forms (k_gemm9.h MODE 1 ... 6)
-    }
+    // everything the plan reads (gemm_plan.h); M, N and row_norm_out are filled in per chunk
+    GemmPlanIn in{};
+    in.K = K; in.act = act != VL2_ACT_NONE; in.swiglu = sw; in.f32 = f32; in.gather = g; in.remap = remap;
+    in.res = d->res != nullptr; in.stats_out = d->stats_out != nullptr; in.norm = d->norm != VL2_NORM_NONE; in.row_norm = d->row_norm != nullptr;
+    in.tile_ctr = d->tile_ctr || d->ws; in.ws = d->ws != nullptr; in.ws_bytes = d->ws_bytes;
+    in.variant = v; in.lab = kLab;
+    in.splitk = (d->flags & VL2_GEMM_SPLITK) != 0;
+    in.persist = (d->flags & VL2_GEMM_PERSISTENT) != 0;
+    in.no_mix = (d->flags & VL2_GEMM_NO_MIX) != 0;
+    in.no_fill = (d->flags & VL2_GEMM_NO_FILL) != 0;
+    in.weave = (d->flags & VL2_GEMM_WEAVE) != 0;
+    in.weave4 = (d->flags & VL2_GEMM_WEAVE4) != 0;
+    in.no_weave4 = (d->flags & VL2_GEMM_NO_WEAVE4) != 0;
+    in.N = N;
+    // the 16 x 16 x 32 kernel: the flag is a wish (ignored where the kernel is not built), variant 16 a demand
+    if (gemm_v16(v) && !gemm_ok16(in)) return fail(VL2_E_UNSUPP, "vl2_gemm: variant 16 (16x16x32 MFMA) is built for plain bf16 outputs without activation / gather / remap / stats_out, N %% 256 == 0");
+    in.mfma16 = want_mfma16(in, (d->flags & VL2_GEMM_MFMA16) != 0);       // decided here, on the whole call; the plan of a chunk takes it as given
     bool need_fin = d->row_norm_out && (d->flags & VL2_GEMM_NO_TICKET);      // A/B: the separate launch as in rounds 3-4
-    ctl.fin = &need_fin;
     GemmArgs a{};
     a.A = (const bf16_t*)d->A; a.W = (const bf16_t*)d->W; a.C = d->C; a.bias = d->bias; a.res = (const bf16_t*)d->res;
     a.a_idx = d->a_idx; a.zero_row = nullptr;
@@ -834,6 +449,7 @@ extern "C" int32_t vl2_gemm(const vl2_gemm_desc* d, void* stream) {
     if (d->row_norm_out && !need_fin) { a.row_norm_out = d->row_norm_out; a.row_ticket = (unsigned*)d->row_ticket; a.norm_out = d->norm_out; a.norm_out_eps = d->norm_out_eps; }
     a.tile_ctr = d->tile_ctr ? (unsigned*)d->tile_ctr : d->ws ? (unsigned*)((char*)d->ws + GEMM6_CTR_OFF) : nullptr;
     if (d->tile_ctr && ((uintptr_t)d->tile_ctr & 7)) return fail(VL2_E_BADARG, "vl2_gemm: tile_ctr must be 8-byte aligned");
+    if (in.persist || (v >= 60 && v <= 81)) in.cus = cu_count();      // only the persistent form's plan reads it
     hipStream_t s = ST(stream);
     // The kernels address A and W through raw buffer resources: 32-bit byte offsets, NUM_RECORDS 2^31 - 1.  Operands beyond
     // that are covered in chunks of rows (A, C, residual, statistics) / columns (W, bias, w_colsum, C columns): e.g. the
@@ -862,7 +478,7 @@ extern "C" int32_t vl2_gemm(const vl2_gemm_desc* d, void* stream) {
                 if (c.stats_out) c.stats_out = c.stats_out + (size_t)(n0 / 64) * 2;
                 if (c.row_norm_out) { c.row_norm_out = nullptr; need_fin = true; }      // a column chunk sees a part of the row's partials only
             }
-            const int32_t rc = gemm_dispatch(c, ctl, act, sw, f32, s);
+            const int32_t rc = gemm_dispatch(c, in, act, d->ws, &need_fin, s);
             if (rc) return rc;
         }
     }
@@ -1056,7 +672,7 @@ extern "C" int32_t vl2_attn_fwd(const void* q, const void* k, const void* v, voi
         if (D != 64 && D != 128) return fail(VL2_E_SHAPE, "vl2_attn_fwd: variant 4 is built for head_dim 64 and 128 (got %d)", D);
         const dim3 b2(512);
         const int lds_bytes = 4 * (2 * 64 * D * 2);
-#define VL2_ATTN_NS2(KERN, GRID) do { lds_attr<KERN>(lds_bytes); hipLaunchKernelGGL(KERN, GRID, b2, lds_bytes, s, a); } while (0)
+#define VL2_ATTN_NS2(KERN, GRID) launch<KERN>(GRID, b2, lds_bytes, s, a)
         if (cls_peel4) VL2_ATTN_NS2((attn2_fwd_kernel<64, false, true, 2>), dim3((nq - 1 + 127) / 128 + ((((nq - 1) & 127) == 0 || ((nq - 1) & 127) > 96) ? 1 : 0), H, B));
         else if (D == 64 && !causal) VL2_ATTN_NS2((attn2_fwd_kernel<64, false, false, 2>), g);
         else if (D == 64 && causal) VL2_ATTN_NS2((attn2_fwd_kernel<64, true, false, 2>), g);
@@ -1128,9 +744,8 @@ static void launch_dwconv_strip(const void* x, void* y, const float* w9c, const 
                                 float eps, hipStream_t s) {
     const int U = H * ((W + DWS_P - 1) / DWS_P), tpf = dws_tpf(H, W), iters = (U + tpf - 1) / tpf;
     const size_t lds = (size_t)9 * C * 2;
-    lds_attr<dwconv_strip_ln_silu_kernel<NVT>>((int)lds);
-    hipLaunchKernelGGL((dwconv_strip_ln_silu_kernel<NVT>), dim3((F * tpf + 1) / 2), dim3(512), lds, s, (const bf16_t*)x, (bf16_t*)y, w9c, lnw, lnb, psum,
-                       F, H, W, C, eps, tpf, iters);
+    launch<dwconv_strip_ln_silu_kernel<NVT>>(dim3((F * tpf + 1) / 2), dim3(512), (int)lds, s, (const bf16_t*)x, (bf16_t*)y, w9c, lnw, lnb, psum,
+                                             F, H, W, C, eps, tpf, iters);
 }
 extern "C" int64_t vl2_dwconv_mean_workspace_bytes(int32_t F, int32_t C) {
     if (F <= 0 || C <= 0) return -1;
@@ -1698,13 +1313,8 @@ extern "C" int32_t vl2_moe_gemm(const void* A, int32_t lda, const void* W, int64
     q.offs = offs; q.counts = counts; q.w_stride = w_stride; q.E = E; q.rt_cap = P / MOE_BM;
     const dim3 grid((unsigned)(q.rt_cap * (N / GEMM_BN)));
     hipStream_t s = ST(stream);
-    if (sw) {
-        lds_attr<moe_gemm_kernel<true>>(GEMML_LDS_BYTES);
-        hipLaunchKernelGGL((moe_gemm_kernel<true>), grid, dim3(512), GEMML_LDS_BYTES, s, q);
-    } else {
-        lds_attr<moe_gemm_kernel<false>>(GEMML_LDS_BYTES);
-        hipLaunchKernelGGL((moe_gemm_kernel<false>), grid, dim3(512), GEMML_LDS_BYTES, s, q);
-    }
+    if (sw) launch<moe_gemm_kernel<true>>(grid, dim3(512), GEMML_LDS_BYTES, s, q);
+    else launch<moe_gemm_kernel<false>>(grid, dim3(512), GEMML_LDS_BYTES, s, q);
     return launched("vl2_moe_gemm");
 }
 extern "C" int32_t vl2_moe_combine(const void* x1, int32_t ldx1, const void* y, int32_t ldy, const int32_t* inv, const float* wts, int32_t S, int32_t k,
