@@ -1,5 +1,9 @@
 """Per-operator parity on MI355X: every libvl2hip.so kernel, called through the C ABI (videollama2_amd.ops ->
-ctypes), against the fp32 oracle of the same op on identical bf16-rounded inputs.  Tolerances: tests/util.py."""
+ctypes), against the fp32 oracle of the same op on identical bf16-rounded inputs.  Tolerances: tests/util.py.
+
+The GEMM tests here are twin equality (one kernel form against variant 1, `torch.equal`) and a relative L2 of variant 1 on random inputs: they
+show that the forms agree with each other.  That the family gives the RIGHT bits -- every form against the fp64 reference on exact inputs, at the
+tile edges, with padded strides and sentinel frames -- is held by tests/test_gpu_gemm_edges.py (tables and reference: tests/gemm_exact.py)."""
 
 import pytest
 import torch
