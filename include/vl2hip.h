@@ -369,6 +369,22 @@ int32_t vl2_attn_append(const void* q, int64_t q_rs, const void* kcache, const v
                         int32_t nh, int32_t nkv, int32_t smax, float scale, float* ws, int64_t ws_bytes, void* stream);
 /* bytes of the workspace vl2_attn_append needs for (P, n, nh) (an upper bound that does not depend on nkv). */
 int64_t vl2_attn_append_ws_bytes(int32_t P, int32_t n, int32_t nh);
+/* Batched decode attention over a SHARED prompt prefix (csrc/k_attn_shared.h; head_dim 128; an OPTIONAL path, never a default).  The B requests
+ * of the step share the keys of positions [0, P) in ONE cache kprefix / vprefix [nkv, prefix_smax, 128]; request b keeps only its own rows in
+ * kown / vown + b*own_bs = [nkv, own_cap, 128], private row = position - P (own_cap a multiple of 64).  qkv, pos_dev, out as
+ * vl2_attn_decode_batched: pos_dev[b] = the absolute position of b's new token (P <= pos_dev[b]); q is roped at it, k_new is roped at it and
+ * appended with v_new at private row pos_dev[b] - P (the bytes vl2_attn_decode appends for that qkv row and position).  cos_t / sin_t hold
+ * rope_rows >= P + own_cap positions.  Three launches: the prefix phase (B * nh/nkv query rows per kv head against one copy of the prefix on
+ * the matrix pipe, split over the prefix keys), the own rows (vl2_attn_decode_batched's 64-key slices) and the combine over the prefix
+ * splits followed by the ceil((pos - P + 1) / 64) own slices.  No atomics, and the prefix split is a function of P alone: a request's output
+ * bits do not depend on B, on its index b or on the other requests.  A request with pos_dev[b] outside [P, P + own_cap) writes nothing.
+ * partial: fp32 workspace of partial_floats >= B * vl2_attn_decode_shared_partial_floats(P, own_cap, nh). */
+int32_t vl2_attn_decode_shared(const void* qkv, const void* kprefix, const void* vprefix, void* kown, void* vown, const float* cos_t,
+                               const float* sin_t, float* partial, int64_t partial_floats, void* out, int32_t B, int64_t qkv_bs, int64_t own_bs,
+                               int64_t out_bs, int32_t nh, int32_t nkv, int32_t P, int32_t prefix_smax, int32_t own_cap, int32_t rope_rows,
+                               const int32_t* pos_dev, float scale, void* stream);
+/* floats of `partial` ONE request takes in vl2_attn_decode_shared: nh * (prefix splits of P + own_cap / 64) * 130 (0 on bad arguments). */
+int64_t vl2_attn_decode_shared_partial_floats(int32_t P, int32_t own_cap, int32_t nh);
 /* greedy argmax (first maximal index) of fp32 logits -> *tok (device int32) and hist[step] if hist != NULL.
  * state != NULL (device int32[2] = {position, step}): hist index = state[1], then both counters advance by one, so the
  * whole decode step is replayable from a hipGraph.  HF:generation/utils.py _sample with do_sample=False. */

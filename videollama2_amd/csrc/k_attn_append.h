@@ -13,6 +13,7 @@
 #include "dev_common.h"
 #include "k_attn.h"
 #include "k_decode.h"
+#include <type_traits>
 
 #define APPEND_MAX_SPLITS 32          // = COMBINE_EARLY: the combine is one memory round trip
 
@@ -24,8 +25,20 @@ struct AppendArgs {
     float scale_log2e;
     float* ws;                        // [nh][n][nsplit][130]
 };
+// SHARED form (the prefix phase of vl2_attn_decode_shared, k_attn_shared.h): the n rows are n REQUESTS of a batched decode step that share
+// the keys [0, P) of one cache.  q / q_rs = the step's un-roped fused qkv rows and their stride: row b is roped here, at pos_dev[b], and
+// rounded through the element type as attn_decode_kernel rounds its qs.  Every prefix key is visible to every row (only the ragged last
+// tile at P is masked); nsplit = the prefix splits.  The partial of (request b, q head, split) goes to ws + b*partial_bs +
+// (head * nsplit_cap + split) * 130: the leading slices of the request's region of the decode `partial` buffer.  A request whose position
+// is outside [P, P + own_cap) writes nothing.
+struct SharedPrefixArgs : AppendArgs {
+    const int* pos_dev; const float* cos_t; const float* sin_t;      // cos / sin: fp32 [positions][64]
+    int own_cap, nsplit_cap;
+    long partial_bs;
+};
 
-__global__ __launch_bounds__(256, 2) void attn_append_kernel(AppendArgs p) {
+template <bool SHARED>
+__global__ __launch_bounds__(256, 2) void attn_append_kernel(std::conditional_t<SHARED, SharedPrefixArgs, AppendArgs> p) {
     constexpr int D = 128, KCH = D / 8, KPT = 64 * KCH / 256, VPT = 32 * KCH / 256, NKS = D / 16, NDB = D / 32;
     constexpr int KS_BYTES = 64 * D * 2, VT_BYTES = D * 128;
     __shared__ __attribute__((aligned(16))) unsigned char lds[KS_BYTES + VT_BYTES];
@@ -33,12 +46,12 @@ __global__ __launch_bounds__(256, 2) void attn_append_kernel(AppendArgs p) {
     unsigned char* const Vt = lds + KS_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
     const int split = blockIdx.x, hk = blockIdx.y, r0 = blockIdx.z * 128;
-    const int R = p.n * p.group, nk = p.P + p.n;
+    const int R = p.n * p.group, nk = SHARED ? p.P : p.P + p.n;
     // keys of this split that any row of the block can see: [ks0, kmax)
     const int ks0 = split * p.chunk;
     const int rlast = (r0 + 127 < R ? r0 + 127 : R - 1);
     int kmax = ks0 + p.chunk < nk ? ks0 + p.chunk : nk;
-    const int lim = p.P + rlast / p.group + 1;
+    const int lim = SHARED ? nk : p.P + rlast / p.group + 1;
     kmax = lim < kmax ? lim : kmax;
     if (ks0 >= kmax) return;                     // no row of the block reaches this split (the combine does not read it)
     const int ntiles = (kmax - ks0 + 63) >> 6;
@@ -48,12 +61,30 @@ __global__ __launch_bounds__(256, 2) void attn_append_kernel(AppendArgs p) {
     const bool wave_live = wr0 < R;
     const int row = wr0 + l31, row_c = row < R ? row : R - 1;
     const int qi = row_c / p.group, hq = hk * p.group + row_c % p.group;
-    const int lim_row = p.P + qi;                                   // last visible key of the row
-    const int lim_wave0 = p.P + (wr0 < R ? wr0 : R - 1) / p.group;  // ... of the wave's first row (the smallest)
+    const int lim_row = SHARED ? p.P - 1 : p.P + qi;                // last visible key of the row
+    const int lim_wave0 = SHARED ? p.P - 1 : p.P + (wr0 < R ? wr0 : R - 1) / p.group;  // ... of the wave's first row (the smallest)
     const bf16_t* Q = p.q + (size_t)qi * p.q_rs + (size_t)hq * D;
     bf16x8 qf[NKS];
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) qf[ks] = *(const bf16x8*)(Q + ks * 16 + hi * 8);
+    bool row_live = true;
+    if constexpr (SHARED) {
+        // the lane holds both halves of its rotate-half pairs: d = 16 ks + 8 hi + j (ks < 4) and d + 64 (ks + 4)
+        const int pos = p.pos_dev[qi];
+        row_live = pos >= p.P && pos - p.P < p.own_cap;
+        const float* cp = p.cos_t + (size_t)(row_live ? pos : p.P) * 64;
+        const float* sp = p.sin_t + (size_t)(row_live ? pos : p.P) * 64;
+#pragma unroll
+        for (int ks = 0; ks < NKS / 2; ++ks)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int d = ks * 16 + hi * 8 + j;
+                float o1, o2;
+                rope_pair(bf2f_s(qf[ks][j]), bf2f_s(qf[ks + NKS / 2][j]), cp[d], sp[d], o1, o2);
+                qf[ks][j] = (short)f2bf(o1);
+                qf[ks + NKS / 2][j] = (short)f2bf(o2);
+            }
+    }
 
     const bf16_t* K = p.k + (size_t)hk * p.smax * D;
     const bf16_t* V = p.v + (size_t)hk * p.smax * D;
@@ -142,7 +173,10 @@ __global__ __launch_bounds__(256, 2) void attn_append_kernel(AppendArgs p) {
             for (int r = 0; r < 16; ++r) mt = fmaxf(mt, sT[kh][r]);
         mt = fmaxf(mt, __shfl_xor(mt, 32)) * c;
         constexpr float THR = 6.0f;              // deferred rescale, as attn_fwd_kernel
-        if (!__all(mt - m <= THR)) {
+        // SHARED: the rows of a wave belong to several requests, so the decision is each row's own (both halves of a row hold the same mt
+        // and m; the branch holds no cross-lane operation) -- a wave vote would let a neighbour's jump move this row's m, and with it
+        // the rounding of its P and its partial
+        if (SHARED ? mt - m > THR : !__all(mt - m <= THR)) {
             const float m_new = fmaxf(fmaxf(m, mt), -1e28f);
             const float alpha = __builtin_amdgcn_exp2f(m - m_new);
             m = m_new;
@@ -179,8 +213,10 @@ __global__ __launch_bounds__(256, 2) void attn_append_kernel(AppendArgs p) {
             }
     }
     // partial of (row, split): lane (q, hi) holds o[d] for d = 32 db + 8 g + 4 hi + j
-    if (!wave_live || row >= R || ks0 > lim_row) return;
-    float* dst = p.ws + (((size_t)hq * p.n + qi) * p.nsplit + split) * 130;
+    if (!wave_live || row >= R || ks0 > lim_row || !row_live) return;
+    float* dst;
+    if constexpr (SHARED) dst = p.ws + (size_t)qi * p.partial_bs + ((size_t)hq * p.nsplit_cap + split) * 130;
+    else dst = p.ws + (((size_t)hq * p.n + qi) * p.nsplit + split) * 130;
     if (hi == 0) *(f32x2*)dst = f32x2{m, l};
 #pragma unroll
     for (int db = 0; db < NDB; ++db)

@@ -38,6 +38,7 @@ static constexpr bool kLab = false;
 #include "k_vit.h"
 #include "k_moe.h"
 #include "k_attn_append.h"
+#include "k_attn_shared.h"
 #include "k_kv8.h"
 
 static thread_local char g_err[512] = "";
@@ -1194,10 +1195,63 @@ extern "C" int32_t vl2_attn_append(const void* q, int64_t q_rs, const void* kcac
     attn_append_split(P, n, group, nkv, chunk, nsplit);
     AppendArgs a{(const bf16_t*)q, (long)q_rs, (const bf16_t*)kcache, (const bf16_t*)vcache, smax, P, n, nh, nkv, group, chunk, nsplit,
                  scale * 1.4426950408889634f, ws};
-    hipLaunchKernelGGL(attn_append_kernel, dim3(nsplit, nkv, (n * group + 127) / 128), dim3(256), 0, ST(stream), a);
+    hipLaunchKernelGGL(attn_append_kernel<false>, dim3(nsplit, nkv, (n * group + 127) / 128), dim3(256), 0, ST(stream), a);
     hipLaunchKernelGGL(attn_append_combine_kernel, dim3(nh, n), dim3(128), 0, ST(stream), (const float*)ws, (bf16_t*)out, (long)o_rs, n, P,
                        chunk, nsplit);
     return launched("vl2_attn_append");
+}
+// Split of the prefix keys for vl2_attn_decode_shared: a pure function of P (the partial layout and the order of a row's sums must not
+// depend on the batch).  At least two 64-key tiles per split (as attn_append_split), at most 24 splits: with up to 8 own slices (512 own
+// rows) the combine stays within COMBINE_EARLY = one memory round trip.
+static void attn_shared_split(int P, int& chunk, int& nps) {
+    const int T = (P + 63) / 64;
+    int tps = (T + 23) / 24;
+    tps = tps > 2 ? tps : 2;
+    chunk = tps * 64;
+    nps = (P + chunk - 1) / chunk;
+}
+extern "C" int64_t vl2_attn_decode_shared_partial_floats(int32_t P, int32_t own_cap, int32_t nh) {
+    if (P <= 0 || own_cap <= 0 || own_cap % 64 || nh <= 0) return 0;
+    int chunk, nps;
+    attn_shared_split(P, chunk, nps);
+    return (int64_t)nh * (nps + own_cap / 64) * 130;
+}
+extern "C" int32_t vl2_attn_decode_shared(const void* qkv, const void* kprefix, const void* vprefix, void* kown, void* vown, const float* cos_t,
+                                          const float* sin_t, float* partial, int64_t partial_floats, void* out, int32_t B, int64_t qkv_bs,
+                                          int64_t own_bs, int64_t out_bs, int32_t nh, int32_t nkv, int32_t P, int32_t prefix_smax, int32_t own_cap,
+                                          int32_t rope_rows, const int32_t* pos_dev, float scale, void* stream) {
+    if (!qkv || !kprefix || !vprefix || !kown || !vown || !cos_t || !sin_t || !partial || !out || !pos_dev || nh <= 0 || nkv <= 0 || B <= 0)
+        return fail(VL2_E_BADARG, "vl2_attn_decode_shared: bad args");
+    if (nh % nkv) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: need nh = nkv*group");
+    if (P <= 0 || P > prefix_smax) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: prefix of %d rows outside the prefix cache (%d)", P, prefix_smax);
+    if ((int64_t)prefix_smax * 128 * 2 >= (1ll << 31)) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: one head's prefix cache spans >= 2 GiB");
+    if (own_cap <= 0 || own_cap % 64) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: own_cap %d must be a positive multiple of 64", own_cap);
+    if ((int64_t)P + own_cap > rope_rows)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: positions up to %lld outside the cos/sin tables (%d rows)", (long long)P + own_cap - 1, rope_rows);
+    if (qkv_bs < ((int64_t)nh + 2 * nkv) * 128 || (qkv_bs & 7) || out_bs < (int64_t)nh * 128 || own_bs < (int64_t)nkv * own_cap * 128 || (own_bs & 7) ||
+        !ALIGNED16(qkv) || !ALIGNED16(kprefix) || !ALIGNED16(vprefix) || !ALIGNED16(kown) || !ALIGNED16(vown))
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: rows must hold their heads' 128 elements at 16-byte alignment, a slot nkv*own_cap rows");
+    const int64_t partial_bs = vl2_attn_decode_shared_partial_floats(P, own_cap, nh);
+    if (partial_floats < partial_bs * B)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: partial of %lld floats, need %lld", (long long)partial_floats, (long long)(partial_bs * B));
+    const int group = nh / nkv;
+    if ((int64_t)nkv * B > 65535 || ((int64_t)B * group + 127) / 128 > 65535) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared: too many requests (%d)", B);
+    int chunk, nps;
+    attn_shared_split(P, chunk, nps);
+    const int nsplit_cap = nps + own_cap / 64;
+    const float sl2 = scale * 1.4426950408889634f;
+    SharedPrefixArgs a{};
+    a.q = (const bf16_t*)qkv; a.q_rs = (long)qkv_bs; a.k = (const bf16_t*)kprefix; a.v = (const bf16_t*)vprefix;
+    a.smax = prefix_smax; a.P = P; a.n = B; a.nh = nh; a.nkv = nkv; a.group = group; a.chunk = chunk; a.nsplit = nps;
+    a.scale_log2e = sl2; a.ws = partial;
+    a.pos_dev = pos_dev; a.cos_t = cos_t; a.sin_t = sin_t; a.own_cap = own_cap; a.nsplit_cap = nsplit_cap; a.partial_bs = (long)partial_bs;
+    hipLaunchKernelGGL(attn_append_kernel<true>, dim3(nps, nkv, (B * group + 127) / 128), dim3(256), 0, ST(stream), a);
+    hipLaunchKernelGGL(attn_decode_own_kernel, dim3(own_cap / 64, nkv * B, (group + 3) / 4), dim3(256), 0, ST(stream), (const bf16_t*)qkv,
+                       (bf16_t*)kown, (bf16_t*)vown, cos_t, sin_t, partial, nh, group, nkv, own_cap, P, nps, nsplit_cap, pos_dev, sl2, (long)qkv_bs,
+                       (long)own_bs, (long)partial_bs);
+    hipLaunchKernelGGL(attn_shared_combine_kernel, dim3(nh, B), dim3(128), 0, ST(stream), (const float*)partial, (bf16_t*)out, P, nps, own_cap,
+                       nsplit_cap, pos_dev, (long)partial_bs, (long)out_bs);
+    return launched("vl2_attn_decode_shared");
 }
 extern "C" int32_t vl2_argmax(const float* logits, int32_t V, int32_t* tok, int32_t* hist, int32_t step, int32_t* state,
                               void* stream) {

@@ -146,10 +146,7 @@ class HipMistralDecoder(nn.Module):
         self.D, self.V, self.eps = l["hidden_size"], l["vocab_size"], l["rms_norm_eps"]
         self.max_seq_len = max_seq_len
         # RoPE tables, fp32, HF MistralRotaryEmbedding: inv_freq = theta^(-2i/d); cos/sin of pos*inv_freq
-        inv = 1.0 / (l["rope_theta"] ** (torch.arange(0, self.hd, 2, dtype=torch.int64).float() / self.hd))
-        fr = torch.arange(max_seq_len, dtype=torch.float32)[:, None] * inv[None, :]
-        self.cos_t = fr.cos().contiguous().to(self._dev)
-        self.sin_t = fr.sin().contiguous().to(self._dev)
+        self.cos_t, self.sin_t = self._rope_tables(max_seq_len)
         self._elem = _lib.elem()
         bf = dict(dtype=_lib.elem_dtype(), device=self._dev)
         self.kcache = [torch.zeros((self.nkv, max_seq_len, self.hd), **bf) for _ in range(self.n_layers)]
@@ -177,6 +174,26 @@ class HipMistralDecoder(nn.Module):
         self.tp_always_reduce = False
         self.decode_fp8 = self.prefill_fp8 = self.decode_mxfp4 = False
         self._fp8_kv, self.kv8 = False, None        # enable_fp8_kv: per layer (k8, v8, ks, vs), the single-sequence fp8 KV cache
+
+    def _rope_tables(self, rows):
+        """cos / sin of pos * inv_freq for positions 0 .. rows-1, fp32 [rows, head_dim / 2] on the device."""
+        inv = 1.0 / (self.cfg["llm"]["rope_theta"] ** (torch.arange(0, self.hd, 2, dtype=torch.int64).float() / self.hd))
+        fr = torch.arange(rows, dtype=torch.float32)[:, None] * inv[None, :]
+        return fr.cos().contiguous().to(self._dev), fr.sin().contiguous().to(self._dev)
+
+    def _step_buffers(self, B, u_cols):
+        """Activations, logits, tokens, positions and per-slot draw settings of a batched decode step for B slots (u: u_cols uniform
+        numbers per slot; temperature 0 = greedy; slot b draws at u[b, sstep[b]])."""
+        bf = dict(dtype=_lib.elem_dtype(), device=self._dev)
+        I = self.cfg["llm"]["intermediate_size"] // self.tp
+        return dict(
+            x0=torch.empty((B, self.D), **bf), x1=torch.empty((B, self.D), **bf), qkv=torch.empty((B, (self.nh + 2 * self.nkv) * self.hd), **bf),
+            o=torch.empty((B, self.nh * self.hd), **bf), a=torch.empty((B, I), **bf),
+            logits=torch.empty((B, self.V), dtype=torch.float32, device=self._dev),
+            tok=torch.zeros((B,), dtype=torch.int32, device=self._dev), pos=torch.zeros((B,), dtype=torch.int32, device=self._dev),
+            samp_T=torch.zeros((B,), dtype=torch.float32, device=self._dev), samp_k=torch.zeros((B,), dtype=torch.int32, device=self._dev),
+            samp_p=torch.ones((B,), dtype=torch.float32, device=self._dev), u=torch.zeros((B, u_cols), dtype=torch.float32, device=self._dev),
+            sstep=torch.zeros((B,), dtype=torch.int32, device=self._dev))
 
     @property
     def decode_format(self):
@@ -636,7 +653,7 @@ class HipMistralDecoder(nn.Module):
         if self._dev.type == "cuda":
             ops.attach_workspace(self._dev)          # fp32 partial sums of the skinny-M GEMMs of a large-batch decode step
         bf = dict(dtype=_lib.elem_dtype(), device=self._dev)
-        smax, I = self.max_seq_len, self.cfg["llm"]["intermediate_size"] // self.tp
+        smax = self.max_seq_len
         if self._fp8_kv:         # the slots in fp8 ONLY (per layer (k8, v8, ks, vs) with a leading slot dimension) + one sequence's 16-bit staging
             self._fp8_kv_refusals()                  # cache, which a request's prefill fills before its rows are quantised into its slot
             caches = dict(kv8=[ops.kv8_alloc((B,), self.nkv, smax, self._dev) for _ in range(self.n_layers)],
@@ -648,14 +665,7 @@ class HipMistralDecoder(nn.Module):
         self._bb = dict(
             B=B, **caches,
             partial=torch.empty((B * self.nh * ((smax + 63) // 64) * 130,), dtype=torch.float32, device=self._dev),
-            x0=torch.empty((B, self.D), **bf), x1=torch.empty((B, self.D), **bf), qkv=torch.empty((B, (self.nh + 2 * self.nkv) * self.hd), **bf),
-            o=torch.empty((B, self.nh * self.hd), **bf), a=torch.empty((B, I), **bf),
-            logits=torch.empty((B, self.V), dtype=torch.float32, device=self._dev),
-            tok=torch.zeros((B,), dtype=torch.int32, device=self._dev), pos=torch.zeros((B,), dtype=torch.int32, device=self._dev),
-            # per-slot draw settings of the sampled step (ops.sample_tokens): temperature 0 = greedy; slot b draws at u[b, sstep[b]]
-            samp_T=torch.zeros((B,), dtype=torch.float32, device=self._dev), samp_k=torch.zeros((B,), dtype=torch.int32, device=self._dev),
-            samp_p=torch.ones((B,), dtype=torch.float32, device=self._dev), u=torch.zeros((B, smax + 1), dtype=torch.float32, device=self._dev),
-            sstep=torch.zeros((B,), dtype=torch.int32, device=self._dev))
+            **self._step_buffers(B, smax + 1))
         return self._bb
 
     def prefill_slot(self, slot, x, logits_out):
@@ -673,7 +683,7 @@ class HipMistralDecoder(nn.Module):
     PREFILL_GROUP_TOKENS = 8192   # rows prefilled in one pass (activation scratch: ~0.6 GB at 7B widths)
     GEMM_BATCH = 5      # from this many sequences on, the decode step runs its projections on MFMA (M = sequences)
 
-    def _decode_kernels_batched(self, nb):
+    def _decode_kernels_batched(self, nb, bb=None, attend=None):
         """One decode step for the nb sequences of the batch: the weights stream ONCE for nb tokens, the attention runs per
         sequence on its own cache slice and position (one launch for all of them).
         nb < GEMM_BATCH: multi-row GEMV (a row is bit-identical to the single-sequence step).  nb >= GEMM_BATCH: the
@@ -685,8 +695,10 @@ class HipMistralDecoder(nn.Module):
         skinny-M step on the dequantised weights).  With enable_mxfp4_decode: the same two paths on the MXFP4 copies, with the same guarantees
         against the solo MXFP4 step and the dequantised weights; lm_head on the 16-bit kernels.
         With enable_fp8_kv the attention of every form above runs on the slots' fp8 caches (one vl2_attn_decode_kv8_batched launch per layer):
-        a row's attention is bit for bit the single-sequence fp8-KV step's."""
-        bb = self._bb
+        a row's attention is bit for bit the single-sequence fp8-KV step's.
+        bb / attend: the step's buffers and its attention callable attend(li, qkv, o) when they are not the slots' (the shared-prefix mode,
+        `_shared_attend`)."""
+        bb = self._bb if bb is None else bb
         if self._fp8_kv:
             self._fp8_kv_refusals()                  # (tp_always_reduce can be set after the slots exist)
         x = bb["x0"][:nb]
@@ -699,30 +711,30 @@ class HipMistralDecoder(nn.Module):
         else:
             f = _Gemv(self, self.decode_format, batched=True)
 
-        def attend(li, qkv, o):
+        def attend_slots(li, qkv, o):
             if self._fp8_kv:
                 return ops.attn_decode_kv8_batched(qkv, tuple(t[:nb] for t in bb["kv8"][li]), self.cos_t, self.sin_t, bb["partial"], o,
                                                    self.nh, self.nkv, bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
             ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, self.nh, self.nkv,
                                     bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
-        self._tokens(f, attend, x, bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb], bb["logits"][:nb])
+        self._tokens(f, attend_slots if attend is None else attend, x, bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb], bb["logits"][:nb])
         bb["pos"][:nb] += 1
 
-    def _sample_rows(self, nb):
+    def _sample_rows(self, nb, bb=None):
         """The draws of slots 0 .. nb-1 in ONE launch from their per-slot settings (samp_T / samp_k / samp_p, u, sstep): greedy slots take the
         argmax, sampled ones draw and advance their sstep."""
-        bb = self._bb
+        bb = self._bb if bb is None else bb
         ops.sample_tokens(bb["logits"][:nb], bb["samp_T"], bb["samp_k"], bb["samp_p"], bb["u"], bb["sstep"], bb["tok"])
 
     @torch.no_grad()
-    def _batched_step(self, nb, sampled=False):
-        bb = self._bb
+    def _batched_step(self, nb, sampled=False, bb=None, attend=None):
+        bb = self._bb if bb is None else bb
         if sampled:
-            self._sample_rows(nb)
+            self._sample_rows(nb, bb)
         else:
             for b in range(nb):
                 ops.argmax(bb["logits"][b], bb["tok"][b:b + 1])
-        self._decode_kernels_batched(nb)
+        self._decode_kernels_batched(nb, bb, attend)
 
     def capture_batch_graph(self, nb, sampled=False):
         """{the draws + the whole batched decode step} as ONE hipGraph per (batch size, sampled) (tokens, positions and the
@@ -741,7 +753,8 @@ class HipMistralDecoder(nn.Module):
         return g
 
     @torch.no_grad()
-    def generate_batch(self, inputs_embeds_list, max_new_tokens=2048, eos_token_id=None, return_logits=False, use_graph=None, sampler=None):
+    def generate_batch(self, inputs_embeds_list, max_new_tokens=2048, eos_token_id=None, return_logits=False, use_graph=None, sampler=None,
+                       shared_prefix=None):
         """Greedy decode of several requests at once (not in the reference, whose eval loops run batch 1 and whose worker
         serialises requests; its padded-batch `prepare_inputs_labels_for_multimodal`, arch.py:227-261, is the nearest thing):
         every request is prefilled on its own (its M is already large), then ALL of them decode together, one token per
@@ -755,7 +768,12 @@ class HipMistralDecoder(nn.Module):
         one ops.sample_token gives on its row); replayed from its own captured graph like the greedy step.
         With enable_fp8_kv the slots hold fp8 rows only, so the requests are prefilled ONE AFTER ANOTHER through the single 16-bit staging
         cache and quantised into their slots (bit-identical to the grouped prefill); what it costs is the fuller GEMM
-        grids of the grouped prefill: short prompts run their projections at a smaller M each."""
+        grids of the grouped prefill: short prompts run their projections at a smaller M each.
+        shared_prefix = x_prefix [P, D] (opt-in): every request's prompt is x_prefix followed by its entry of `inputs_embeds_list` (its
+        suffix, at least one row).  The prefix is prefilled ONCE, its KV rows are kept once and read once per step for all requests
+        (`_generate_batch_shared`)."""
+        if shared_prefix is not None:
+            return self._generate_batch_shared(shared_prefix, inputs_embeds_list, max_new_tokens, eos_token_id, return_logits, use_graph, sampler)
         nb = len(inputs_embeds_list)
         if use_graph is None:
             use_graph = self._dev.type == "cuda" and self.tp == 1
@@ -798,11 +816,16 @@ class HipMistralDecoder(nn.Module):
         flush()
         bb["pos"][:nb].copy_(torch.tensor(lens, dtype=torch.int32))
         max_new_tokens = min(max_new_tokens, self.max_seq_len - max(lens) + 1)
-        outs, done, all_logits = [[] for _ in range(nb)], [False] * nb, []
         use_graph = use_graph and max(lens) < self.max_seq_len          # a full cache leaves nothing to replay (see generate)
         graph = self.capture_batch_graph(nb, sampled) if use_graph else None
         if graph is not None:                                                # capture clobbered nothing: state was restored
             bb["pos"][:nb].copy_(torch.tensor(lens, dtype=torch.int32))
+        return self._batched_loop(bb, nb, max_new_tokens, eos, return_logits, graph, sampled, lambda: self._decode_kernels_batched(nb))
+
+    def _batched_loop(self, bb, nb, max_new_tokens, eos, return_logits, graph, sampled, forward):
+        """The token loop of the batched paths on the step buffers bb: draws, stop checks on the host, then `forward()` (or the captured
+        graph, which holds the draws and the forward of a step)."""
+        outs, done, all_logits = [[] for _ in range(nb)], [False] * nb, []
         for step in range(max_new_tokens):
             if return_logits:
                 all_logits.append(bb["logits"][:nb].clone())
@@ -810,7 +833,7 @@ class HipMistralDecoder(nn.Module):
             if graph is not None and not last:
                 graph.replay()                                               # draws(step) + forward of the new tokens
             elif sampled:
-                self._sample_rows(nb)
+                self._sample_rows(nb, bb)
             else:
                 for b in range(nb):
                     ops.argmax(bb["logits"][b], bb["tok"][b:b + 1])
@@ -822,9 +845,102 @@ class HipMistralDecoder(nn.Module):
             if all(done) or last:
                 break
             if graph is None:
-                self._decode_kernels_batched(nb)
+                forward()
         res = [torch.tensor(o, dtype=torch.long, device=self._dev) for o in outs]
         return (res, torch.stack(all_logits)) if return_logits else res
+
+    # ------------------------------------------------------------------ batched decode over a shared prompt prefix
+    def _shared_prefix_refusals(self):
+        if self._fp8_kv:
+            raise NotImplementedError("shared-prefix decode: the fp8 KV cache is on (the prefix phase and extend read 16-bit rows): call "
+                                      "enable_fp8_kv(False) first")
+        if self.tp > 1 or self.tp_group is not None or self.tp_local is not None or self.tp_always_reduce:
+            raise NotImplementedError("shared-prefix decode: single-rank decoders only (extend and the prefix phase are not built for a "
+                                      "tensor-parallel shard)")
+        if self.hd != 128:
+            raise NotImplementedError(f"shared-prefix decode: head_dim 128 only (this decoder has {self.hd})")
+        if self.prefill_fp8:
+            raise NotImplementedError("shared-prefix decode: the suffixes run through extend, which runs the 16-bit projections: call "
+                                      "enable_fp8_prefill(False) first")
+
+    def _ensure_shared(self, B, P, own_cap):
+        """Step buffers of the shared-prefix mode: the private caches [B, nkv, own_cap, 128] per layer (a request's rows from position P
+        on -- not max_seq_len rows), the partial workspace for (P, own_cap) and the per-request step state of `_ensure_batch`."""
+        sp = getattr(self, "_sp", None)
+        if sp is not None and (sp["B"], sp["P"], sp["own_cap"]) == (B, P, own_cap):
+            return sp
+        self._sp = None                               # (the old caches go before the new ones are allocated)
+        if self._dev.type == "cuda":
+            ops.attach_workspace(self._dev)
+        bf = dict(dtype=_lib.elem_dtype(), device=self._dev)
+        cos_t, sin_t = self.cos_t, self.sin_t
+        if P + own_cap > self.max_seq_len:            # own_cap is rounded up to the slice: the launch covers rows no request reaches
+            cos_t, sin_t = self._rope_tables(P + own_cap)
+        self._sp = dict(
+            B=B, P=P, own_cap=own_cap, cos_t=cos_t, sin_t=sin_t,
+            k=[torch.zeros((B, self.nkv, own_cap, self.hd), **bf) for _ in range(self.n_layers)],
+            v=[torch.zeros((B, self.nkv, own_cap, self.hd), **bf) for _ in range(self.n_layers)],
+            partial=torch.empty((B * ops.shared_partial_floats(P, own_cap, self.nh),), dtype=torch.float32, device=self._dev),
+            **self._step_buffers(B, own_cap + 1))
+        return self._sp
+
+    def _shared_attend(self, sp, nb):
+        """The attention callable of a shared-prefix step: prefix phase + own rows + combine (one ops.attn_decode_shared call per layer) on
+        the decoder's single-sequence cache (rows [0, P): the shared prefix) and the private caches of sp."""
+        def attend(li, qkv, o):
+            ops.attn_decode_shared(qkv, self.kcache[li], self.vcache[li], sp["k"][li][:nb], sp["v"][li][:nb], sp["cos_t"], sp["sin_t"],
+                                   sp["partial"], o, self.nh, self.nkv, sp["P"], sp["pos"][:nb], self.hd ** -0.5)
+        return attend
+
+    @torch.no_grad()
+    def _generate_batch_shared(self, x_prefix, suffixes, max_new_tokens, eos_token_id, return_logits, use_graph, sampler):
+        """generate_batch(shared_prefix=x_prefix): request b's prompt is x_prefix [P, D] ++ suffixes[b] [n_b, D].
+        The prefix is prefilled once (the unchanged `prefill`) into the decoder's single-sequence cache, which IS the shared prefix.  Each
+        suffix then runs through `extend(start_pos=P)` on that cache (existing kernels, existing bits); its rows [P, P + n_b) of every
+        layer are copied to rows [0, n_b) of the request's private cache, its last row's logits to the request's logits row, and the next
+        request overwrites the rows from P on.  The private caches hold own_cap = (longest suffix + max_new_tokens, rounded up to 64) rows
+        per request.  The decode loop is generate_batch's; its step is `_decode_kernels_batched` with `_shared_attend`, captured as one
+        hipGraph per call (P is a launch constant).  Projections: 16-bit, fp8 or MXFP4 decode weights, untouched.  A request's attention
+        agrees with the plain batched step's to 16-bit rounding, not to the bit: the prefix sums run on the matrix pipe."""
+        self._shared_prefix_refusals()
+        _lib.check_elem(self._elem, type(self).__name__)
+        nb, P = len(suffixes), int(x_prefix.shape[0])
+        lens = [int(x.shape[0]) for x in suffixes]
+        if nb == 0 or P <= 0 or min(lens) <= 0:
+            raise ValueError("shared-prefix decode: need a prefix of at least one row and, for every request, a suffix of at least one row")
+        if P + max(lens) > self.max_seq_len:
+            raise ValueError(f"sequence length {P + max(lens)} exceeds the KV cache ({self.max_seq_len})")
+        if use_graph is None:
+            use_graph = self._dev.type == "cuda"
+        sampled = sampler is not None
+        max_new_tokens = min(max_new_tokens, self.max_seq_len - (P + max(lens)) + 1)
+        if sampled:
+            T_, tk_, tp_ = float(sampler[0]), int(sampler[1]), float(sampler[2])
+            if not T_ > 0.0 or tk_ < 0 or not tp_ > 0.0:
+                raise ValueError(f"sampler: need temperature > 0, top_k >= 0, top_p > 0 (got {T_}, {tk_}, {tp_})")
+            gen = sampler[3] if len(sampler) > 3 else None
+            n_u = max_new_tokens + 1
+            u_rows = torch.stack([torch.rand((n_u,), device=self._dev, generator=gen) for _ in range(nb)]).contiguous()
+        eos = eos_set(eos_token_id)
+        sp = self._ensure_shared(nb, P, ops.shared_own_cap(max(lens), max_new_tokens))
+        if sampled:
+            sp["samp_T"].fill_(T_); sp["samp_k"].fill_(tk_); sp["samp_p"].fill_(tp_)
+            sp["u"][:, :n_u].copy_(u_rows); sp["sstep"].zero_()
+        self.prefill(x_prefix)
+        for b, xb in enumerate(suffixes):
+            self.extend(xb, start_pos=P, logits_out=sp["logits"][b])
+            for li in range(self.n_layers):
+                sp["k"][li][b, :, :lens[b]].copy_(self.kcache[li][:, P:P + lens[b]])
+                sp["v"][li][b, :, :lens[b]].copy_(self.vcache[li][:, P:P + lens[b]])
+        self.pos = P                                  # the resident rows a later extend may build on: the prefix
+        pos0 = torch.tensor([P + n for n in lens], dtype=torch.int32)
+        sp["pos"].copy_(pos0)
+        attend = self._shared_attend(sp, nb)
+        graph = None
+        if use_graph and P + max(lens) < self.max_seq_len and max_new_tokens > 1:
+            step = lambda: self._batched_step(nb, sampled, sp, attend)
+            graph = self._capture(step, step, (sp["tok"], sp["pos"], sp["logits"], sp["sstep"]))
+        return self._batched_loop(sp, nb, max_new_tokens, eos, return_logits, graph, sampled, lambda: self._decode_kernels_batched(nb, sp, attend))
 
 
 HipQwen2Decoder = HipMistralDecoder      # same decoder; the q/k/v bias is picked up from the state dict (weights.pack_decoder)
@@ -867,7 +983,12 @@ class HipMixtralDecoder(HipMistralDecoder):
         raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")
 
     def generate_batch(self, *args, **kwargs):
+        if kwargs.get("shared_prefix") is not None:
+            self._shared_prefix_refusals()
         raise NotImplementedError("MoE (mixtral) decoder: batched decoding not built")
+
+    def _shared_prefix_refusals(self):
+        raise NotImplementedError("MoE (mixtral) decoder: shared-prefix decode is not built (its batched decoding is not)")
 
     def _ensure_batch(self, B, owner=None):
         raise NotImplementedError("MoE (mixtral) decoder: batched / continuous decoding not built")

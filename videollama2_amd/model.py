@@ -48,6 +48,26 @@ def resolve_sampler(kwargs, generation_config=None):
     return (temperature, top_k, top_p, kwargs.get("generator", None))
 
 
+def common_prefix_tokens(ids_lists, media_lists, sentinels, media_equal):
+    """Host side of `generate_shared`: the number t of leading tokens that every request shares, so that ids[:t] can be prefilled once.
+    A modal sentinel counts as shared only when the media it stands for (the k-th entry of each request's media list) are equal for all
+    requests (`media_equal`); otherwise the prefix is cut BEFORE that sentinel.  Every request keeps at least one token of its own (its
+    last row's logits start its decode), so t <= min(len) - 1."""
+    first = ids_lists[0]
+    n = min(len(x) for x in ids_lists) - 1
+    t = mk = 0
+    while t < n:
+        a = first[t]
+        if any(x[t] != a for x in ids_lists[1:]):
+            break
+        if a in sentinels:
+            if any(mk >= len(m) for m in media_lists) or any(not media_equal(media_lists[0][mk], m[mk]) for m in media_lists[1:]):
+                break
+            mk += 1
+        t += 1
+    return t
+
+
 class VideoLLaMA2Hip(nn.Module):
     def __init__(self, cfg, state_dict, device="cuda", max_seq_len=4096, image_processor=None, n_llm_layers=None,
                  mm_projector_type=None, sharder=None, tp_group=None):
@@ -450,3 +470,33 @@ class VideoLLaMA2Hip(nn.Module):
                                            eos_token_id=kwargs.get("eos_token_id", None),
                                            return_logits=kwargs.get("return_logits", False), sampler=sampler)
 
+
+    @torch.no_grad()
+    def generate_shared(self, requests, **kwargs):
+        """One video, several questions (opt-in): `requests` and the result as `generate_batch`.  The token ids the
+        requests have in common (`common_prefix_tokens`: sentinels compared by the media they stand for) are the shared prefix: the tower
+        and the connector run ONCE, the prefix is spliced and prefilled once, and every request prefills and keeps only its own rows
+        (`HipMistralDecoder.generate_batch(shared_prefix=...)`).  Requests that share no leading token, or that still hold a modal tag
+        after the common prefix (their visual inputs differ), are not merged: the call is `generate_batch(requests)`."""
+        sent = set(MODAL_INDEX_MAP.values())
+        ids_l = [(ids[0] if ids.dim() == 2 else ids).tolist() for ids, _ in requests]
+        media = [list(images) if images is not None else [] for _, images in requests]
+        t = common_prefix_tokens(ids_l, media, sent, self._media_equal)
+        if t == 0 or any(tok in sent for x in ids_l for tok in x[t:]):
+            return self.generate_batch(requests, **kwargs)
+        self.decoder._shared_prefix_refusals()               # before the encoder or any other kernel runs
+        sampler = resolve_sampler(kwargs, getattr(self, "generation_config", None))
+        n_sent = sum(1 for tok in ids_l[0][:t] if tok in sent)
+        feats = []
+        if n_sent:
+            f = self.encode_images_or_videos(media[0][:n_sent])
+            feats = [f[k] for k in range(n_sent)]
+        x_prefix = self._embed_suffix(ids_l[0][:t], feats, 0)
+        suffixes = []
+        for x in ids_l:
+            emb = torch.empty((len(x) - t, self.decoder.D), dtype=_lib.elem_dtype(), device=self._dev)
+            self._embed_ids(torch.tensor(x[t:], dtype=torch.int64).to(self._dev), emb)
+            suffixes.append(emb)
+        return self.decoder.generate_batch(suffixes, max_new_tokens=kwargs.get("max_new_tokens", 2048), eos_token_id=kwargs.get("eos_token_id", None),
+                                           return_logits=kwargs.get("return_logits", False), use_graph=kwargs.get("use_graph", None),
+                                           sampler=sampler, shared_prefix=x_prefix)

@@ -610,6 +610,69 @@ def attn_append(q, kcache, vcache, out, P, nh, nkv, scale, ws=None):
     return out
 
 
+def shared_prefix_splits(P):
+    """Splits of the prefix keys [0, P) in vl2_attn_decode_shared (csrc/vl2_abi.hip attn_shared_split): a function of P alone -- at least
+    two 64-key tiles per split, at most 24 splits."""
+    tiles = (P + 63) // 64
+    chunk = max((tiles + 23) // 24, 2) * 64
+    return (P + chunk - 1) // chunk
+
+
+def shared_own_cap(longest_suffix, max_new_tokens):
+    """Rows of a request's private cache in the shared-prefix mode: its suffix and every token it may feed, rounded up to the 64-key slice."""
+    return (int(longest_suffix) + int(max_new_tokens) + 63) // 64 * 64
+
+
+def shared_live_slices(P, pos):
+    """Slices the combine of vl2_attn_decode_shared merges for a request whose new token sits at absolute position pos >= P."""
+    return shared_prefix_splits(P) + (pos - P + 64) // 64
+
+
+def shared_partial_floats(P, own_cap, nh):
+    """Floats ONE request takes in the `partial` workspace of vl2_attn_decode_shared (= vl2_attn_decode_shared_partial_floats)."""
+    return nh * (shared_prefix_splits(P) + own_cap // 64) * 130
+
+
+def attn_decode_shared(qkv, kprefix, vprefix, kown, vown, cos_t, sin_t, partial, out, nh, nkv, P, pos_dev, scale):
+    """include/vl2hip.h vl2_attn_decode_shared: the batched decode attention of B = qkv.shape[0] requests that share the keys of positions
+    [0, P) in ONE cache kprefix / vprefix [nkv, smax, 128] and keep their own rows, from position P on, in kown / vown [B, nkv, own_cap, 128]
+    (private row = position - P; own_cap a multiple of 64).  qkv [B, (nh+2nkv)*128] un-roped, pos_dev int32 [B] absolute positions, out
+    [B, nh*128]; partial: fp32, at least B * shared_partial_floats(P, own_cap, nh) floats.  Everything is checked here, before the library
+    is called."""
+    P = int(P)
+    if qkv.dim() != 2 or nh <= 0 or nkv <= 0 or nh % nkv or qkv.shape[1] != (nh + 2 * nkv) * 128:
+        raise ValueError(f"attn_decode_shared: qkv must be [B, (nh + 2 nkv) * 128] with nh = nkv * group, got {tuple(qkv.shape)} for nh {nh}, nkv {nkv}")
+    B = qkv.shape[0]
+    if kprefix.dim() != 3 or kprefix.shape[0] != nkv or kprefix.shape[2] != 128 or vprefix.shape != kprefix.shape or \
+            not (kprefix.is_contiguous() and vprefix.is_contiguous()):
+        raise ValueError(f"attn_decode_shared: the prefix caches must be contiguous [nkv, smax, 128], got {tuple(kprefix.shape)}, {tuple(vprefix.shape)}")
+    if not 0 < P <= kprefix.shape[1]:
+        raise ValueError(f"attn_decode_shared: a prefix of {P} rows is outside the prefix cache ({kprefix.shape[1]} rows)")
+    if kown.dim() != 4 or kown.shape[0] < B or kown.shape[1] != nkv or kown.shape[3] != 128 or vown.shape != kown.shape or \
+            vown.stride() != kown.stride() or not kown[0].is_contiguous():
+        raise ValueError(f"attn_decode_shared: the private caches must be [B, nkv, own_cap, 128] with contiguous slots, got {tuple(kown.shape)}, "
+                         f"{tuple(vown.shape)}")
+    own_cap = kown.shape[2]
+    if own_cap % 64:
+        raise ValueError(f"attn_decode_shared: own_cap {own_cap} must be a multiple of 64")
+    if cos_t.shape != sin_t.shape or cos_t.dim() != 2 or cos_t.shape[1] != 64 or P + own_cap > cos_t.shape[0]:
+        raise ValueError(f"attn_decode_shared: positions up to {P + own_cap - 1} need cos / sin tables [>= {P + own_cap}, 64], got {tuple(cos_t.shape)}")
+    if pos_dev.numel() < B or out.dim() != 2 or out.shape[0] < B or out.shape[1] != nh * 128:
+        raise ValueError(f"attn_decode_shared: need {B} positions and out [B, nh * 128], got {pos_dev.numel()}, {tuple(out.shape)}")
+    need = B * shared_partial_floats(P, own_cap, nh)
+    if partial.numel() < need:
+        raise ValueError(f"attn_decode_shared: partial holds {partial.numel()} floats, need {need}")
+    e = _lib.elem_dtype()
+    for t, dt, name in ((qkv, e, "qkv"), (kprefix, e, "kprefix"), (vprefix, e, "vprefix"), (kown, e, "kown"), (vown, e, "vown"), (out, e, "out"),
+                        (cos_t, torch.float32, "cos_t"), (sin_t, torch.float32, "sin_t"), (partial, torch.float32, "partial"),
+                        (pos_dev, torch.int32, "pos_dev")):
+        _chk(t, dt, name)
+    _lib.call("vl2_attn_decode_shared", _p(qkv), _p(kprefix), _p(vprefix), _p(kown), _p(vown), _p(cos_t), _p(sin_t), _p(partial), partial.numel(),
+              _p(out), B, qkv.stride(0), kown.stride(0), out.stride(0), nh, nkv, P, kprefix.shape[1], own_cap, cos_t.shape[0], _p(pos_dev),
+              float(scale), _stream())
+    return out
+
+
 def argmax(logits, tok, hist=None, step=0, state=None):
     _lib.call("vl2_argmax", _p(logits), logits.numel(), _p(tok), _p(hist), step, _p(state), _stream())
 
