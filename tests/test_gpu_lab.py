@@ -177,6 +177,23 @@ def test_lab_attn_decode_fused_combine_equals_two_kernels(ops, nh, nkv, smax, po
         assert cnt.tolist() == [((pos + 64) // 64) * ((group + 3) // 4)] * nkv
 
 
+@pytest.mark.parametrize("group,nkv", [(4, 2), (7, 2), (8, 2)])
+def test_lab_attn_decode_fused_on_exact_key_selecting_inputs(ops, group, nkv):
+    """vl2_attn_decode_fused on the decode table of tests/attn_exact.py: every position, through all three regimes of
+    the elected combine (attn_combine_head<true, 64>: two columns per thread, no early path), against the same expected bits as vl2_attn_decode
+    -- the fp64 softmax rounded once --, with the poisoned cache rows, partial workspace and output sentinel of those cases."""
+    from tests import attn_exact as A
+    errs = []
+    for pos in A.DECODE_POS:
+        st = A.DecodeState(group, nkv, pos, torch.bfloat16, DEV)
+        cnt = torch.zeros(nkv, dtype=torch.int32, device=DEV)
+        for rnd in range(st.rounds):
+            err = A.run_decode(ops, st, "cap_smax", rnd, fused_cnt=cnt)
+            if err:
+                errs.append(err)
+            assert cnt.tolist() == [((pos + 64) // 64) * ((group + 3) // 4)] * nkv, pos
+    assert not errs, f"{len(errs)} launches failed:\n" + "\n".join(errs[:12])
+
 
 
 def test_lab_decode_step_forms_equal_the_default(ops):
