@@ -385,6 +385,24 @@ int32_t vl2_attn_decode_shared(const void* qkv, const void* kprefix, const void*
                                const int32_t* pos_dev, float scale, void* stream);
 /* floats of `partial` ONE request takes in vl2_attn_decode_shared: nh * (prefix splits of P + own_cap / 64) * 130 (0 on bad arguments). */
 int64_t vl2_attn_decode_shared_partial_floats(int32_t P, int32_t own_cap, int32_t nh);
+/* ---- paged KV cache for the batched decode step (csrc/k_attn_paged.h; additions of ABI 7; head_dim 128; an OPTIONAL layout, never a default:
+ * it changes where rows live, not one sum).  A PAGE is 64 consecutive positions of one sequence, all kv heads, one layer, K or V:
+ * [nkv, 64, 128] 16-bit elements, the bytes the contiguous cache holds for those rows (K roped and rounded).  kpool / vpool = [n_pages] pages
+ * (one pool pair per layer; a page id names the same page in every layer's pools).  page_table: device int32 [B, table_bs]; entry j of row b
+ * is the page of positions [64 j, 64 j + 64) of sequence b, -1 = not assigned.
+ * vl2_attn_decode_paged: vl2_attn_decode_batched with the rows of a 64-key slice read from (and the new token's rows appended to) the page the
+ *   table names for it: the same grid, partial layout [B][nh][ceil(ctx_cap/64)][130], arithmetic and combine -- bit for bit that call on
+ *   contiguous copies of the same rows.  seq_cap (a multiple of 64, <= 64 * table_bs) takes smax's place: cos_t / sin_t hold at least seq_cap
+ *   rows, ctx_cap <= seq_cap.  A sequence writes NOTHING if pos_dev[b] >= seq_cap; a 64-key slice whose page id is outside [0, n_pages)
+ *   touches neither pool (nor appends).  In both cases the sequence's output row is unspecified: the host discards it.
+ * vl2_kv_page_scatter: rows [p0, p1) (p0 == p1: nothing) of ONE sequence's contiguous 16-bit caches k16 / v16 [nkv, smax, 128] -> the pages
+ *   named by its table row (table_row: ceil(smax / 64) entries), K and V in one launch, byte for byte; rows whose page id is outside
+ *   [0, n_pages) are skipped and nothing else in the pools is written. */
+int32_t vl2_attn_decode_paged(const void* qkv, void* kpool, void* vpool, const int32_t* page_table, const float* cos_t, const float* sin_t,
+                              float* partial, void* out, int32_t B, int64_t qkv_bs, int32_t table_bs, int32_t n_pages, int64_t out_bs, int32_t nh,
+                              int32_t nkv, int32_t seq_cap, const int32_t* pos_dev, int32_t ctx_cap, float scale, void* stream);
+int32_t vl2_kv_page_scatter(const void* k16, const void* v16, void* kpool, void* vpool, const int32_t* table_row, int32_t nkv, int32_t smax,
+                            int32_t n_pages, int32_t p0, int32_t p1, void* stream);
 /* greedy argmax (first maximal index) of fp32 logits -> *tok (device int32) and hist[step] if hist != NULL.
  * state != NULL (device int32[2] = {position, step}): hist index = state[1], then both counters advance by one, so the
  * whole decode step is replayable from a hipGraph.  HF:generation/utils.py _sample with do_sample=False. */

@@ -4,11 +4,14 @@
 the greedy decode loop on its own KV cache and returns the NEW token ids, as HF `generate` does on the
 `inputs_embeds` path.  Per-layer math follows HF:models/mistral/modeling_mistral.py (RMSNorm fp32 statistics,
 rotate-half RoPE theta=1e6, causal GQA attention, SwiGLU), executed by libvl2hip.so kernels only."""
+import gc
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib, ops
+from .paging import PagePool, pages_needed, parked_row, table_row
 from .weights import pack_decoder
 
 
@@ -174,6 +177,7 @@ class HipMistralDecoder(nn.Module):
         self.tp_always_reduce = False
         self.decode_fp8 = self.prefill_fp8 = self.decode_mxfp4 = False
         self._fp8_kv, self.kv8 = False, None        # enable_fp8_kv: per layer (k8, v8, ks, vs), the single-sequence fp8 KV cache
+        self._paged_kv, self._n_pages = False, 0    # enable_paged_kv: the batched paths keep their slots' rows in pages of a shared pool
 
     def _rope_tables(self, rows):
         """cos / sin of pos * inv_freq for positions 0 .. rows-1, fp32 [rows, head_dim / 2] on the device."""
@@ -267,6 +271,8 @@ class HipMistralDecoder(nn.Module):
         arithmetic and never the default: with it off every path keeps its bits; tests/fp8kv_oracle.py defines the format."""
         if on:
             self._fp8_kv_refusals()
+        if on and getattr(self, "_paged_kv", False):
+            raise NotImplementedError("fp8 KV cache: the paged KV cache is on (its pages hold 16-bit rows): call enable_paged_kv(0, False) first")
         busy = getattr(self, "_bb_busy", None)
         if busy is not None and busy.in_flight():
             raise RuntimeError("enable_fp8_kv: a ContinuousBatcher holds requests in flight on this decoder's slots, whose caches would change "
@@ -286,6 +292,54 @@ class HipMistralDecoder(nn.Module):
         """Rows [0, n) of every layer's 16-bit caches (a prefill's) -> the fp8 caches kv8 (per layer (k8, v8, ks, vs))."""
         for li in range(self.n_layers):
             ops.kv_quant(kcache[li], vcache[li], kv8[li], 0, n)
+
+    # ------------------------------------------------------------------ paged KV cache of the batched paths (DESIGN.md section 19)
+    @property
+    def paged_kv(self):
+        """Whether the batched paths keep their slots' KV rows in pages of a shared pool (enable_paged_kv)."""
+        return self._paged_kv
+
+    def kv_page_bytes(self):
+        """Bytes of ONE page over all layers, K and V: n_layers * 2 * nkv * 64 * 128 * 2 (8.39 MB at 7B; 64 pages = a 4096-row slot)."""
+        return self.n_layers * 2 * self.nkv * ops.KV_PAGE_ROWS * 128 * 2
+
+    def _paged_kv_refusals(self):
+        if self.tp > 1 or self.tp_group is not None or self.tp_local is not None or self.tp_always_reduce:
+            raise NotImplementedError("paged KV cache: single-rank decoders only (no tensor-parallel shard's slots are built on pages): build "
+                                      "the decoder without a tensor-parallel group, or keep the contiguous slots")
+        if self.hd != 128:
+            raise NotImplementedError(f"paged KV cache: head_dim 128 only (this decoder has {self.hd}): keep the contiguous slots")
+        if self._fp8_kv:
+            raise NotImplementedError("paged KV cache: the fp8 KV cache is on (the pages hold 16-bit rows): call enable_fp8_kv(False) first")
+
+    @torch.no_grad()
+    def enable_paged_kv(self, n_pages, on=True):
+        """OPTIONAL layout, never the default: the batched paths (`generate_batch`, ContinuousBatcher) keep their slots' 16-bit KV rows in
+        PAGES of 64 positions drawn from one pool of `n_pages` pages per layer (csrc/k_attn_paged.h) instead of a
+        private cache of max_seq_len rows per slot: a request holds ceil(min(S + max_new, max_seq_len) / 64) pages, `kv_page_bytes()` each,
+        whatever max_seq_len is.  Page 0 is the parking page of the slots that hold no request, so n_pages - 1 pages serve requests.  It
+        changes where rows live and not one sum: every batched result is bit for bit the contiguous slots' (with it off every path keeps
+        its bits and its launches).  A request is prefilled into one 16-bit staging cache (the unchanged `prefill`) and its rows are copied
+        into its pages.  Switching drops every captured batch graph and the slot buffers; it is refused while a batcher holds requests in
+        flight.  The single-sequence paths (`generate`, `extend`, the prefix cache) keep their contiguous cache and are untouched.
+        Tensor parallelism, head_dim != 128, Mixtral, the fp8 KV cache (each switch refuses the other) and
+        `generate_batch(shared_prefix=...)` raise NotImplementedError.  Not built: growing a reservation page by page, preemption."""
+        if on:
+            self._paged_kv_refusals()
+            if int(n_pages) < 2:
+                raise ValueError(f"enable_paged_kv: n_pages {n_pages}: page 0 is the parking page, a request needs at least one more")
+        busy = getattr(self, "_bb_busy", None)
+        if busy is not None and busy.in_flight():
+            raise RuntimeError("enable_paged_kv: a ContinuousBatcher holds requests in flight on this decoder's slots, whose rows would change "
+                               "layout under them: drain it (run()) first")
+        self._paged_kv, self._n_pages = bool(on), int(n_pages) if on else 0
+        self._invalidate_graphs()
+        self._bb = None                              # the slots are in the other layout: the next batched call allocates them again
+        return self
+
+    def _set_table_rows(self, slot0, rows):
+        """Rows slot0 .. of the device page table <- `rows` (lists of pages_per_seq ids each): one small H2D copy."""
+        self._bb["table"][slot0:slot0 + len(rows)].copy_(torch.tensor(rows, dtype=torch.int32))
 
     def _make_w8(self):
         """The fp8 copies of the packed projections (shared by the decode and the prefill switch).  The stage descriptor is rebuilt with
@@ -530,7 +584,10 @@ class HipMistralDecoder(nn.Module):
     def _capture(warm_up, step, keep):
         """`step` as a hipGraph: warm-up outside capture on a side stream (first-launch attribute calls, the allocator), capture in
         thread-local mode (a RCCL watchdog thread may be polling events), then the tensors in `keep`, which the warm-up advanced, are
-        restored."""
+        restored.  Python's cyclic garbage collector is held off while the stream captures: a pass that starts inside the capture may
+        finalise a dead decoder (a decoder and its ContinuousBatcher refer to each other, so a dropped pair waits for the collector) and
+        with it that decoder's captured graphs and pools, which the runtime does not survive in the middle of a capture (seen: the process
+        aborted in a collection that began inside capture_batch_graph).  torch.cuda.graph no longer collects before it captures."""
         saved = [t.clone() for t in keep]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -539,8 +596,14 @@ class HipMistralDecoder(nn.Module):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            step()
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                step()
+        finally:
+            if gc_on:
+                gc.enable()
         for t, s in zip(keep, saved):
             t.copy_(s)
         torch.cuda.synchronize()
@@ -659,6 +722,16 @@ class HipMistralDecoder(nn.Module):
             caches = dict(kv8=[ops.kv8_alloc((B,), self.nkv, smax, self._dev) for _ in range(self.n_layers)],
                           stage=([torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
                                  [torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)]))
+        elif self._paged_kv:     # the pools, the page table (every slot parked on page 0), the allocator + one sequence's 16-bit staging cache;
+            self._paged_kv_refusals()                # no tensor of max_seq_len rows per slot
+            pps = (smax + ops.KV_PAGE_ROWS - 1) // ops.KV_PAGE_ROWS
+            pools = [ops.kv_pool_alloc(self._n_pages, self.nkv, self._dev) for _ in range(self.n_layers)]
+            # the table covers 64 * pps >= max_seq_len positions and the kernel wants cos / sin rows for all of them
+            cos_t, sin_t = (self.cos_t, self.sin_t) if pps * ops.KV_PAGE_ROWS == smax else self._rope_tables(pps * ops.KV_PAGE_ROWS)
+            caches = dict(kpool=[p[0] for p in pools], vpool=[p[1] for p in pools], pool=PagePool(self._n_pages), pages_per_seq=pps,
+                          table=torch.tensor([parked_row(pps)] * B, dtype=torch.int32).to(self._dev), cos_t=cos_t, sin_t=sin_t,
+                          stage=([torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
+                                 [torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)]))
         else:
             caches = dict(k=[torch.zeros((B, self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
                           v=[torch.zeros((B, self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)])
@@ -670,12 +743,17 @@ class HipMistralDecoder(nn.Module):
 
     def prefill_slot(self, slot, x, logits_out):
         """Prefill one request (inputs_embeds x [S, D]) into batch slot `slot`: rows [0, S) of its caches, the last row's fp32 logits in
-        logits_out.  fp8 KV: through the 16-bit staging cache, whose rows [0, S) are then quantised into the slot.  The decoder's own
-        single-sequence position is left alone."""
+        logits_out.  fp8 KV: through the 16-bit staging cache, whose rows [0, S) are then quantised into the slot.  Paged KV: through the
+        staging cache likewise, its rows then copied into the pages the slot's table row names (assigned by the caller beforehand).  The
+        decoder's own single-sequence position is left alone."""
         bb, own_pos = self._bb, self.pos
         if self._fp8_kv:
             self.prefill(x, cache=bb["stage"], logits_out=logits_out)
             self._quant_rows(*bb["stage"], [tuple(t[slot] for t in kv8) for kv8 in bb["kv8"]], x.shape[0])
+        elif self._paged_kv:     # through the 16-bit staging cache (the prefill keeps its bits), then its rows [0, S) into the slot's pages
+            self.prefill(x, cache=bb["stage"], logits_out=logits_out)
+            for li in range(self.n_layers):
+                ops.kv_page_scatter(bb["stage"][0][li], bb["stage"][1][li], bb["kpool"][li], bb["vpool"][li], bb["table"][slot], 0, x.shape[0])
         else:
             self.prefill(x, cache=([k[slot] for k in bb["k"]], [v[slot] for v in bb["v"]]), logits_out=logits_out)
         self.pos = own_pos
@@ -696,11 +774,15 @@ class HipMistralDecoder(nn.Module):
         against the solo MXFP4 step and the dequantised weights; lm_head on the 16-bit kernels.
         With enable_fp8_kv the attention of every form above runs on the slots' fp8 caches (one vl2_attn_decode_kv8_batched launch per layer):
         a row's attention is bit for bit the single-sequence fp8-KV step's.
+        With enable_paged_kv the attention of every form above reads and appends the slots' rows in their pages (one vl2_attn_decode_paged
+        launch per layer, the page table read from the device): bit for bit the contiguous slots' step.
         bb / attend: the step's buffers and its attention callable attend(li, qkv, o) when they are not the slots' (the shared-prefix mode,
         `_shared_attend`)."""
         bb = self._bb if bb is None else bb
         if self._fp8_kv:
             self._fp8_kv_refusals()                  # (tp_always_reduce can be set after the slots exist)
+        if self._paged_kv and attend is None:
+            self._paged_kv_refusals()
         x = bb["x0"][:nb]
         ops.embed_rows(bb["tok"][:nb], self.w["embed"], x)
         if nb >= self.GEMM_BATCH:
@@ -715,6 +797,9 @@ class HipMistralDecoder(nn.Module):
             if self._fp8_kv:
                 return ops.attn_decode_kv8_batched(qkv, tuple(t[:nb] for t in bb["kv8"][li]), self.cos_t, self.sin_t, bb["partial"], o,
                                                    self.nh, self.nkv, bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
+            if self._paged_kv:
+                return ops.attn_decode_paged(qkv, bb["kpool"][li], bb["vpool"][li], bb["table"], bb["cos_t"], bb["sin_t"], bb["partial"], o,
+                                             self.nh, self.nkv, bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
             ops.attn_decode_batched(qkv, bb["k"][li][:nb], bb["v"][li][:nb], self.cos_t, self.sin_t, bb["partial"], o, self.nh, self.nkv,
                                     bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
         self._tokens(f, attend_slots if attend is None else attend, x, bb["x1"][:nb], bb["qkv"][:nb], bb["o"][:nb], bb["a"][:nb], bb["logits"][:nb])
@@ -771,12 +856,18 @@ class HipMistralDecoder(nn.Module):
         grids of the grouped prefill: short prompts run their projections at a smaller M each.
         shared_prefix = x_prefix [P, D] (opt-in): every request's prompt is x_prefix followed by its entry of `inputs_embeds_list` (its
         suffix, at least one row).  The prefix is prefilled ONCE, its KV rows are kept once and read once per step for all requests
-        (`_generate_batch_shared`)."""
+        (`_generate_batch_shared`).
+        With enable_paged_kv the slots' rows live in pages of the shared pool: every request reserves pages_needed(S_b, max_new_tokens,
+        max_seq_len) pages up front (a pool that cannot hold them all raises ValueError before any kernel runs) and gives them back when
+        the call returns, on an error as well; the requests are prefilled ONE AFTER ANOTHER through the single 16-bit staging cache and
+        copied into their pages (bit-identical to the grouped prefill; the cost is the grouped prefill's fuller GEMM grids, as under
+        enable_fp8_kv).  Tokens and logits are bit for bit the contiguous slots'.  shared_prefix is refused."""
         if shared_prefix is not None:
             return self._generate_batch_shared(shared_prefix, inputs_embeds_list, max_new_tokens, eos_token_id, return_logits, use_graph, sampler)
         nb = len(inputs_embeds_list)
         if use_graph is None:
             use_graph = self._dev.type == "cuda" and self.tp == 1
+        u_rows = None
         if sampler is not None:
             T_, tk_, tp_ = float(sampler[0]), int(sampler[1]), float(sampler[2])
             if not T_ > 0.0 or tk_ < 0 or not tp_ > 0.0:
@@ -786,13 +877,39 @@ class HipMistralDecoder(nn.Module):
             u_rows = torch.stack([torch.rand((n_u,), device=self._dev, generator=gen) for _ in range(nb)]).contiguous()
         eos = eos_set(eos_token_id)
         bb = self._ensure_batch(nb)
+        run = lambda: self._generate_batch_slots(bb, inputs_embeds_list, max_new_tokens, eos, return_logits, use_graph, sampler, u_rows)
+        if self._paged_kv:       # reserve every request's pages first; they go back to the pool when the call returns, however it returns
+            lens = [int(x.shape[0]) for x in inputs_embeds_list]
+            if max(lens) > self.max_seq_len:
+                raise ValueError(f"sequence length {max(lens)} exceeds the KV cache ({self.max_seq_len})")
+            need = [pages_needed(n, max_new_tokens, self.max_seq_len) for n in lens]
+            pool = bb["pool"]
+            if sum(need) > pool.n_free:
+                raise ValueError(f"paged KV cache: the {nb} requests need {sum(need)} pages ({need}), the pool has {pool.n_free} free "
+                                 f"(of {pool.n_pages - 1}; enable_paged_kv(n_pages))")
+            pages = [pool.alloc(n) for n in need]
+            try:
+                self._set_table_rows(0, [table_row(pg, bb["pages_per_seq"]) for pg in pages])
+                return run()
+            finally:
+                for pg in pages:
+                    pool.free(pg)
+                self._set_table_rows(0, [parked_row(bb["pages_per_seq"])] * nb)
+        return run()
+
+    def _generate_batch_slots(self, bb, inputs_embeds_list, max_new_tokens, eos, return_logits, use_graph, sampler, u_rows):
+        """generate_batch on the slot buffers bb (paged KV: the requests' pages are in the table already): prefill, then the token loop."""
+        nb = len(inputs_embeds_list)
         sampled = sampler is not None
         if sampled:
+            T_, tk_, tp_ = float(sampler[0]), int(sampler[1]), float(sampler[2])
+            n_u = u_rows.shape[1]
             bb["samp_T"][:nb].fill_(T_); bb["samp_k"][:nb].fill_(tk_); bb["samp_p"][:nb].fill_(tp_)
             bb["u"][:nb, :n_u].copy_(u_rows); bb["sstep"][:nb].zero_()
         # prompts are prefilled together in groups of <= PREFILL_GROUP_TOKENS rows (bit-identical to one by one)
         lens, group, gtok = [], [], 0
-        caches = None if self._fp8_kv else [([k[b] for k in bb["k"]], [v[b] for v in bb["v"]]) for b in range(nb)]
+        staged = self._fp8_kv or self._paged_kv      # the slots are not 16-bit contiguous caches: one by one through the staging cache
+        caches = None if staged else [([k[b] for k in bb["k"]], [v[b] for v in bb["v"]]) for b in range(nb)]
 
         def flush():
             if group:
@@ -801,7 +918,7 @@ class HipMistralDecoder(nn.Module):
                 group.clear()
 
         for b, xb in enumerate(inputs_embeds_list):
-            if self._fp8_kv:                         # one by one through the staging cache
+            if staged:
                 if xb.shape[0] > self.max_seq_len:
                     raise ValueError(f"sequence length {xb.shape[0]} exceeds the KV cache ({self.max_seq_len})")
                 self.prefill_slot(b, xb, bb["logits"][b])
@@ -851,6 +968,9 @@ class HipMistralDecoder(nn.Module):
 
     # ------------------------------------------------------------------ batched decode over a shared prompt prefix
     def _shared_prefix_refusals(self):
+        if getattr(self, "_paged_kv", False):
+            raise NotImplementedError("shared-prefix decode: the paged KV cache is on (the private caches of this mode are contiguous): call "
+                                      "enable_paged_kv(0, False) first")
         if self._fp8_kv:
             raise NotImplementedError("shared-prefix decode: the fp8 KV cache is on (the prefix phase and extend read 16-bit rows): call "
                                       "enable_fp8_kv(False) first")
@@ -978,6 +1098,10 @@ class HipMixtralDecoder(HipMistralDecoder):
     def enable_fp8_kv(self, on=True):
         raise NotImplementedError("MoE (mixtral) decoder: the fp8 KV cache is not built for it (its step runs the MoE GEMVs on the 16-bit "
                                   "cache): keep the 16-bit cache")
+
+    def enable_paged_kv(self, n_pages, on=True):
+        raise NotImplementedError("MoE (mixtral) decoder: the paged KV cache is not built for it (its batched decoding is not): keep the "
+                                  "contiguous cache")
 
     def prefill_batch(self, xs, caches, logits_out):
         raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")

@@ -426,6 +426,14 @@ class VideoLLaMA2Hip(nn.Module):
         self._prefix_rec = None                      # the resident rows a prefix-cache call recorded are gone
         return self
 
+    def enable_paged_kv(self, n_pages, on=True):
+        """OPTIONAL layout, never the default: the batched paths (`generate_batch`, the padded-batch `generate`, `batcher()`) keep their slots'
+        KV rows in pages of 64 positions from one pool of n_pages pages (`HipMistralDecoder.enable_paged_kv`): slot memory
+        follows the requests' lengths, not max_seq_len, and every result keeps its bits.  The single-sequence `generate` and its prefix cache are
+        untouched.  Tensor-parallel decoders, Mixtral, head_dim != 128, the fp8 KV cache and generate_shared refuse it."""
+        self.decoder.enable_paged_kv(n_pages, on)
+        return self
+
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None):
         """Continuous batching over this model (serving.ModelBatcher): submit (input_ids, images) requests at any time, `step()`
         decodes one token for everything in flight, admission / retirement happen between steps."""

@@ -589,6 +589,89 @@ def attn_decode_kv8_batched(qkv, kv8, cos_t, sin_t, partial, out, nh, nkv, pos_d
     return out
 
 
+KV_PAGE_ROWS = 64      # positions per page of the paged KV cache = keys per slice of the decode attention (csrc/k_attn_paged.h)
+
+
+def kv_pool_alloc(n_pages, nkv, device):
+    """One layer's page pools (include/vl2hip.h, csrc/k_attn_paged.h) as (kpool, vpool): [n_pages, nkv, 64, 128] elements of the build's
+    16-bit type, zero (page 0, the parking page, must hold finite rows)."""
+    n_pages = int(n_pages)
+    if n_pages < 1 or nkv <= 0:
+        raise ValueError(f"kv_pool_alloc: need n_pages >= 1 (the parking page) and nkv > 0, got {n_pages}, {nkv}")
+    mk = lambda: torch.zeros((n_pages, nkv, KV_PAGE_ROWS, 128), dtype=_lib.elem_dtype(), device=device)
+    return mk(), mk()
+
+
+def _dtypes(who, *triples):
+    """dtype checks that come before the shape checks (and before `_chk`, which asks for a device tensor first)."""
+    for t, dt, name in triples:
+        if t.dtype != dt:
+            raise TypeError(f"{who}: {name} must be {dt}, got {t.dtype}")
+
+
+def _chk_pools(who, kpool, vpool, nkv=None):
+    _dtypes(who, (kpool, _lib.elem_dtype(), "kpool"), (vpool, _lib.elem_dtype(), "vpool"))
+    if kpool.dim() != 4 or tuple(kpool.shape[2:]) != (KV_PAGE_ROWS, 128) or vpool.shape != kpool.shape or (nkv is not None and kpool.shape[1] != nkv):
+        raise ValueError(f"{who}: the pools must be [n_pages, nkv, 64, 128], got {tuple(kpool.shape)}, {tuple(vpool.shape)}")
+    if not (kpool.is_contiguous() and vpool.is_contiguous()):
+        raise ValueError(f"{who}: the pools' pages must be contiguous")
+    return kpool.shape[0], kpool.shape[1]
+
+
+def kv_page_scatter(kcache, vcache, kpool, vpool, table_row, p0, p1):
+    """include/vl2hip.h vl2_kv_page_scatter: rows [p0, p1) of one sequence's contiguous 16-bit caches [nkv, smax, 128] -> the pages its table
+    row names (int32 [>= ceil(smax / 64)], contiguous), byte for byte; rows whose page id is outside the pools are skipped."""
+    e = _lib.elem_dtype()
+    _dtypes("kv_page_scatter", (kcache, e, "kcache"), (vcache, e, "vcache"), (table_row, torch.int32, "table_row"))
+    n_pages, nkv = _chk_pools("kv_page_scatter", kpool, vpool)
+    if kcache.dim() != 3 or kcache.shape[0] != nkv or kcache.shape[2] != 128 or vcache.shape != kcache.shape or \
+            not (kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError(f"kv_page_scatter: need contiguous 16-bit caches [nkv = {nkv}, smax, 128], got {tuple(kcache.shape)}, {tuple(vcache.shape)}")
+    smax = kcache.shape[1]
+    if table_row.dim() != 1 or not table_row.is_contiguous() or table_row.numel() < (smax + KV_PAGE_ROWS - 1) // KV_PAGE_ROWS:
+        raise ValueError(f"kv_page_scatter: the table row must be a contiguous int32 vector of at least {(smax + KV_PAGE_ROWS - 1) // KV_PAGE_ROWS} "
+                         f"entries, got {tuple(table_row.shape)}")
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 <= p1 <= smax:
+        raise ValueError(f"kv_page_scatter: rows [{p0}, {p1}) outside the cache ({smax})")
+    for t, name in ((kcache, "kcache"), (vcache, "vcache"), (kpool, "kpool"), (vpool, "vpool"), (table_row, "table_row")):
+        _chk(t, t.dtype, name)
+    _lib.call("vl2_kv_page_scatter", _p(kcache), _p(vcache), _p(kpool), _p(vpool), _p(table_row), nkv, smax, n_pages, p0, p1, _stream())
+
+
+def attn_decode_paged(qkv, kpool, vpool, table, cos_t, sin_t, partial, out, nh, nkv, pos_dev, ctx_cap, scale):
+    """include/vl2hip.h vl2_attn_decode_paged: `attn_decode_batched` on the paged cache.  qkv [B, (nh+2nkv)*128] un-roped, pools
+    [n_pages, nkv, 64, 128], table int32 [>= B, pages_per_seq] (row b: request b's pages, -1 = not assigned), out [B, nh*128], pos_dev int32
+    [B]; seq_cap = 64 * pages_per_seq, which cos_t / sin_t must cover; partial: B * nh * ceil(ctx_cap/64) * 130 floats.  Bit for bit
+    `attn_decode_batched` on contiguous copies of the same rows.  Everything is checked here, before the library is called."""
+    if qkv.dim() != 2 or nh <= 0 or nkv <= 0 or nh % nkv or qkv.shape[1] != (nh + 2 * nkv) * 128:
+        raise ValueError(f"attn_decode_paged: qkv must be [B, (nh + 2 nkv) * 128] with nh = nkv * group, got {tuple(qkv.shape)} for nh {nh}, nkv {nkv}")
+    B = qkv.shape[0]
+    e = _lib.elem_dtype()
+    operands = ((qkv, e, "qkv"), (out, e, "out"), (cos_t, torch.float32, "cos_t"), (sin_t, torch.float32, "sin_t"),
+                (partial, torch.float32, "partial"), (pos_dev, torch.int32, "pos_dev"), (table, torch.int32, "table"))
+    _dtypes("attn_decode_paged", *operands)
+    n_pages, _ = _chk_pools("attn_decode_paged", kpool, vpool, nkv)
+    if table.dim() != 2 or table.shape[0] < B or table.shape[1] < 1 or table.stride(1) != 1:
+        raise ValueError(f"attn_decode_paged: the page table must be int32 [>= {B}, pages_per_seq], got {tuple(table.shape)}")
+    seq_cap = table.shape[1] * KV_PAGE_ROWS
+    ctx_cap = int(ctx_cap)
+    if not 0 < ctx_cap <= seq_cap:
+        raise ValueError(f"attn_decode_paged: ctx_cap {ctx_cap} outside the table's {seq_cap} positions")
+    if cos_t.shape != sin_t.shape or cos_t.dim() != 2 or cos_t.shape[1] != 64 or cos_t.shape[0] < seq_cap or not (cos_t.is_contiguous() and sin_t.is_contiguous()):
+        raise ValueError(f"attn_decode_paged: positions up to {seq_cap - 1} need contiguous cos / sin tables [>= {seq_cap}, 64], got {tuple(cos_t.shape)}")
+    if pos_dev.numel() < B or out.dim() != 2 or out.shape[0] < B or out.shape[1] != nh * 128:
+        raise ValueError(f"attn_decode_paged: need {B} positions and out [B, nh * 128], got {pos_dev.numel()}, {tuple(out.shape)}")
+    need = B * nh * ((ctx_cap + 63) // 64) * 130
+    if partial.numel() < need:
+        raise ValueError(f"attn_decode_paged: partial holds {partial.numel()} floats, need {need}")
+    for t, dt, name in operands + ((kpool, e, "kpool"), (vpool, e, "vpool")):
+        _chk(t, dt, name)
+    _lib.call("vl2_attn_decode_paged", _p(qkv), _p(kpool), _p(vpool), _p(table), _p(cos_t), _p(sin_t), _p(partial), _p(out), B, qkv.stride(0),
+              table.stride(0), n_pages, out.stride(0), nh, nkv, seq_cap, _p(pos_dev), ctx_cap, float(scale), _stream())
+    return out
+
+
 _APPEND_WS = {}
 
 

@@ -1,0 +1,85 @@
+"""Host side of the paged KV cache (kernels: csrc/k_attn_paged.h): the page allocator, a request's reservation and the
+admission rule of the continuous batcher.  Pure Python: nothing here touches a device, so `decoder.py` and `serving.py` share it and the
+CPU tests call it without a decoder.
+
+A page is 64 consecutive positions of one sequence (all kv heads, every layer, K and V: one id names them all).  Page 0 is the PARKING page:
+it is never handed out, and the table row of a slot that holds no request points its entry 0 at it, so that a step computed for such a slot
+at position 0 reads and writes finite, harmless rows."""
+
+PAGE_ROWS = 64
+PARKING_PAGE = 0
+
+
+def pages_needed(S, max_new, max_seq_len):
+    """Pages a request of S prompt rows that may feed max_new tokens reserves: ceil(min(S + max_new, max_seq_len) / 64) -- every row it
+    can write before it retires, the cache end included."""
+    rows = min(int(S) + int(max_new), int(max_seq_len))
+    return (rows + PAGE_ROWS - 1) // PAGE_ROWS
+
+
+def table_row(pages, pages_per_seq):
+    """A request's row of the page table as a list: its pages in position order, -1 behind them."""
+    if len(pages) > pages_per_seq:
+        raise ValueError(f"{len(pages)} pages do not fit a table row of {pages_per_seq}")
+    return list(pages) + [-1] * (pages_per_seq - len(pages))
+
+
+def parked_row(pages_per_seq):
+    """The row of a slot that holds no request: entry 0 = the parking page, the rest not assigned."""
+    return table_row([PARKING_PAGE], pages_per_seq)
+
+
+class PagePool:
+    """The free list over pages 1 .. n_pages - 1 (page 0 is the parking page).  Deterministic: `alloc` hands out the lowest free ids first, so
+    a run repeats its page placement."""
+
+    def __init__(self, n_pages):
+        n_pages = int(n_pages)
+        if n_pages < 1:
+            raise ValueError(f"PagePool: n_pages {n_pages}: the pool holds at least the parking page")
+        self.n_pages = n_pages
+        self._free = set(range(1, n_pages))
+
+    @property
+    def n_free(self):
+        return len(self._free)
+
+    def alloc(self, n):
+        """n page ids, lowest free first.  Raises (and takes none) if fewer than n are free."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"PagePool.alloc: {n} pages")
+        if n > len(self._free):
+            raise RuntimeError(f"PagePool.alloc: {n} pages needed, {len(self._free)} free (of {self.n_pages - 1})")
+        ids = sorted(self._free)[:n]
+        self._free.difference_update(ids)
+        return ids
+
+    def free(self, ids):
+        """Give pages back.  Page 0, an id outside the pool, an id that is free already and a repeated id are refused, and then none is freed."""
+        ids = [int(i) for i in ids]
+        for i in ids:
+            if i == PARKING_PAGE:
+                raise ValueError("PagePool.free: page 0 is the parking page, it is never handed out")
+            if not 0 < i < self.n_pages:
+                raise ValueError(f"PagePool.free: page {i} is not of this pool (1 .. {self.n_pages - 1})")
+            if i in self._free:
+                raise ValueError(f"PagePool.free: page {i} is free already (double free)")
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"PagePool.free: a page is named twice in {ids} (double free)")
+        self._free.update(ids)
+
+
+def admit_fifo(needs, free_slots, free_pages):
+    """The continuous batcher's admission decision for one step.  needs: the reservations (pages) of the waiting requests in submission
+    order; free_slots / free_pages: what the step has to give.  Strict FIFO: the head of the queue is admitted only when a slot is free AND
+    the pool holds its whole reservation; otherwise admission stops for this step -- nobody behind it is admitted, however small.
+    Returns how many requests from the head of the queue are admitted."""
+    n = 0
+    for need in needs:
+        if free_slots <= 0 or need > free_pages:
+            break
+        free_slots -= 1
+        free_pages -= need
+        n += 1
+    return n

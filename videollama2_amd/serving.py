@@ -18,15 +18,17 @@ import itertools
 import torch
 
 from .decoder import eos_set
+from .paging import admit_fifo, pages_needed, parked_row, table_row
 
 
 class _Request:
-    __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done", "sampler", "u")
+    __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done", "sampler", "u", "need", "pages")
 
     def __init__(self, rid, x, max_new, streamer, criteria, sampler=None, u=None):
         self.rid, self.x, self.max_new, self.streamer, self.criteria = rid, x, max_new, streamer, criteria
         self.sampler, self.u = sampler, u              # (temperature, top_k, top_p) and the request's uniform numbers, or None: greedy
         self.tokens, self.slot, self.done = [], None, False
+        self.need, self.pages = 0, None                # paged KV: the reservation (pages) and, once admitted, the page ids
 
 
 class ContinuousBatcher:
@@ -38,7 +40,13 @@ class ContinuousBatcher:
     slot on the weights then selected, and the decoder's cache_epoch is bumped as for any toggle.
     fp8 KV cache (decoder.enable_fp8_kv()): the slots hold fp8 rows only (0.52 x the memory), a request is prefilled into the decoder's 16-bit
     staging cache and quantised into its slot, and the steps attend on the fp8 rows -- a request's tokens equal its solo fp8-KV decode.  That
-    switch changes the slots' format, so the decoder refuses it while requests are in flight."""
+    switch changes the slots' format, so the decoder refuses it while requests are in flight.
+    paged KV cache (decoder.enable_paged_kv(n_pages)): the slots' rows live in pages of 64 positions from one shared pool, so max_slots costs a
+    table row each and a request holds pages_needed(S, max_new, max_seq_len) pages from admission to retirement.  Admission is strict FIFO on
+    the WHOLE reservation (`paging.admit_fifo`): the head of the queue joins only when a slot is free and the pool holds all its pages,
+    otherwise nobody is admitted in that step -- so no request can run out of pages in flight and the step's graph replays untouched (it reads
+    the page table from the device).  A request's tokens are bit for bit the contiguous slots'.  A request that can never fit the pool is
+    refused at `submit`.  Not built: growing a reservation page by page, preemption.  The decoder refuses the switch with requests in flight."""
 
     def __init__(self, decoder, max_slots=4, eos_token_id=None, use_graph=None):
         if decoder.tp > 1:
@@ -76,22 +84,37 @@ class ContinuousBatcher:
         if crit is not None and not isinstance(crit, (list, tuple)):
             crit = [crit]
         max_new = min(int(max_new_tokens), self.dec.max_seq_len - S + 1)
+        need = 0
+        if self.dec.paged_kv:            # its whole reservation; one that the pool can never hold would block the queue for ever
+            need = pages_needed(S, max_new, self.dec.max_seq_len)
+            if need > self.dec._n_pages - 1:
+                raise ValueError(f"paged KV cache: the request needs {need} pages ({S} prompt rows + {max_new} new tokens), the pool serves "
+                                 f"{self.dec._n_pages - 1} (enable_paged_kv(n_pages); page 0 is the parking page)")
         u = None
         if sampler is not None:
             u = torch.rand((max_new,), device=self.dec._dev, generator=sampler[3])
             sampler = sampler[:3]
         r = _Request(next(self._ids), inputs_embeds, max_new, streamer, crit, sampler, u)
+        r.need = need
         self.waiting.append(r)
         return r.rid
 
     def _admit(self):
         bb, dec = self.bb, self.dec
+        paged = dec.paged_kv
+        if paged:                # strict FIFO on whole reservations: how many requests from the head of the queue join in this step
+            free = sum(r is None for r in self.slots)
+            take = admit_fifo([r.need for r in self.waiting], free, bb["pool"].n_free)
         for slot in range(self.max_slots):
-            if not self.waiting:
+            if not self.waiting or (paged and take == 0):
                 return
             if self.slots[slot] is not None:
                 continue
             r = self.waiting.popleft()
+            if paged:            # its pages into the slot's table row (one small H2D copy; the rest of the row is -1), before its prefill's rows go there
+                take -= 1
+                r.pages = bb["pool"].alloc(r.need)
+                dec._set_table_rows(slot, [table_row(r.pages, bb["pages_per_seq"])])
             dec.prefill_slot(slot, r.x, bb["logits"][slot])                       # rows [0, S) of the slot's cache (fp8 KV: quantised from the staging cache)
             bb["pos"][slot:slot + 1].fill_(r.x.shape[0])
             T, k, p = r.sampler if r.sampler is not None else (0.0, 0, 1.0)                # temperature 0: a greedy slot
@@ -154,6 +177,10 @@ class ContinuousBatcher:
             r.streamer.end()
         self.finished[r.rid] = torch.tensor(r.tokens, dtype=torch.long, device=self.dec._dev)
         self.slots[slot] = None
+        if r.pages is not None:          # paged KV: the pages go back to the pool (dirty: whoever gets them overwrites what it reads) and the
+            self.bb["pool"].free(r.pages)            # slot's row points at the parking page again
+            r.pages = None
+            self.dec._set_table_rows(slot, [parked_row(self.bb["pages_per_seq"])])
 
     def in_flight(self):
         return sum(r is not None for r in self.slots) + len(self.waiting)
