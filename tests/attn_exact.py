@@ -354,10 +354,15 @@ def expected(ref64, elem):
     return ref64.to(elem)
 
 
-def first_diff(y, exp):
-    bad = torch.nonzero((y != exp) | y.isnan()).flatten()
+def first_bad(y, exp):
+    """Indices of the flat outputs that differ from the exact ones (a NaN differs from everything)."""
+    return torch.nonzero((y != exp) | y.isnan()).flatten()
+
+
+def first_diff(y, exp, hd=HD):
+    bad = first_bad(y, exp)
     i = int(bad[0])
-    return f"{bad.numel()} of {y.numel()} outputs differ, first at head {i // HD} dim {i % HD}: got {y[i].item()!r}, exact {exp[i].item()!r}"
+    return f"{bad.numel()} of {y.numel()} outputs differ, first at head {i // hd} dim {i % hd}: got {y[i].item()!r}, exact {exp[i].item()!r}"
 
 
 # ---------------------------------------------------------------------------------------------------------------- vl2_attn_decode

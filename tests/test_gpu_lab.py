@@ -133,6 +133,25 @@ def test_lab_causal_attention_without_the_hidden_tile_skip(ops):
         assert torch.equal(outs[3], outs[5]), (S, nh, nkv, off)
 
 
+def _variant5_cases():
+    from tests import attn_fwd_exact as F
+    return [c for c in F.all_cases() if c.table in ("CAUSAL_S", "EXTEND") or F.is_cls_shape(c)]
+
+
+@pytest.mark.parametrize("table", ["CAUSAL_S", "EXTEND", "FULL_64"])
+def test_lab_attention_variant_5_on_exact_key_selecting_inputs(ops, table):
+    """vl2_attn_fwd variant 5 (attn2_fwd_kernel<.., SKIP = false>: the one-stream causal head_dim 128 kernel computing the tiles the mask hides
+    from a whole wave, and the class-token peel with the plain grid order) on the CAUSAL_S and EXTEND tables and the class-token shapes of
+    FULL_64 of tests/attn_fwd_exact.py: the same expected bits as every other variant -- the fp64 softmax rounded once --
+    with the poisoned rows and the sentinel frame of those cases."""
+    from tests import attn_fwd_exact as F
+    errs = []
+    for c in _variant5_cases():
+        if c.table == table:
+            errs += F.run_case(ops, c, torch.bfloat16, DEV, variants=(5,))
+    assert not errs, f"{len(errs)} launches failed:\n" + "\n".join(errs[:12])
+
+
 def test_lab_gemm_stream_k_variant(ops):
     """Stream-K form (tuning knob 2): partial tiles cross workgroups through the caller-owned workspace with an
     agent-scope release/acquire hand-off; repeated launches screen for stale reads.  fp32 sums in a different order."""

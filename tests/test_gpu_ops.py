@@ -3,7 +3,13 @@ ctypes), against the fp32 oracle of the same op on identical bf16-rounded inputs
 
 The GEMM tests here are twin equality (one kernel form against variant 1, `torch.equal`) and a relative L2 of variant 1 on random inputs: they
 show that the forms agree with each other.  That the family gives the RIGHT bits -- every form against the fp64 reference on exact inputs, at the
-tile edges, with padded strides and sentinel frames -- is held by tests/test_gpu_gemm_edges.py (tables and reference: tests/gemm_exact.py)."""
+tile edges, with padded strides and sentinel frames -- is held by tests/test_gpu_gemm_edges.py (tables and reference: tests/gemm_exact.py).
+
+Likewise the vl2_attn_fwd tests here are a whole-tensor relative L2 on random inputs and twin comparisons between variants: they show that the
+forms agree with each other and with the oracle to a norm, which one wrong row or one extra key in several hundred does not move.  The RIGHT
+bits -- every kernel instance against the fp64 softmax on exact key-selecting inputs, at the wave / tile / block edges, the class-token shapes,
+nk short of the diagonal, padded strides, NaN past nk and sentinel frames, and graded weights per (row, head) -- are held by
+tests/test_gpu_attn_fwd_edges.py (tables and reference: tests/attn_fwd_exact.py)."""
 
 import pytest
 import torch
