@@ -403,6 +403,22 @@ int32_t vl2_attn_decode_paged(const void* qkv, void* kpool, void* vpool, const i
                               int32_t nkv, int32_t seq_cap, const int32_t* pos_dev, int32_t ctx_cap, float scale, void* stream);
 int32_t vl2_kv_page_scatter(const void* k16, const void* v16, void* kpool, void* vpool, const int32_t* table_row, int32_t nkv, int32_t smax,
                             int32_t n_pages, int32_t p0, int32_t p1, void* stream);
+/* ---- a shared prompt prefix held ONCE in the page pool (csrc/k_attn_paged_shared.h; additions of ABI 7; head_dim 128; OPTIONAL).  Only whole
+ * pages are shared: P is a positive multiple of 64, prefix_pages (device int32 [P / 64]) names the page of positions [64 j, 64 j + 64) for every
+ * request, and request b's own rows from position P on live in the pages page_table[b * table_bs + P / 64 + s], s < own_cap / 64.
+ * vl2_attn_decode_shared_paged: vl2_attn_decode_shared with the prefix tiles and the own slices read through those page ids (the new token's
+ *   rows are appended to the own page that holds pos_dev[b]) -- bit for bit that call on contiguous copies of the same rows; partial as there
+ *   (vl2_attn_decode_shared_partial_floats(P, own_cap, nh) per request).  P / 64 + own_cap / 64 <= table_bs; cos_t / sin_t hold
+ *   rope_rows >= P + own_cap positions.  A request with pos_dev[b] outside [P, P + own_cap) writes nothing; an own slice whose page id is
+ *   outside [0, n_pages) touches neither pool; a prefix id outside [0, n_pages) reads no memory.  In the last two cases outputs are unspecified.
+ * vl2_kv_page_gather: the inverse of vl2_kv_page_scatter: rows [p0, p1) of the pages table_row names -> ONE sequence's contiguous caches
+ *   k16 / v16 [nkv, smax, 128], byte for byte; rows whose page id is outside [0, n_pages) are skipped and nothing else is written. */
+int32_t vl2_attn_decode_shared_paged(const void* qkv, void* kpool, void* vpool, const int32_t* page_table, const int32_t* prefix_pages,
+                                     const float* cos_t, const float* sin_t, float* partial, int64_t partial_floats, void* out, int32_t B,
+                                     int64_t qkv_bs, int32_t table_bs, int32_t n_pages, int64_t out_bs, int32_t nh, int32_t nkv, int32_t P,
+                                     int32_t own_cap, int32_t rope_rows, const int32_t* pos_dev, float scale, void* stream);
+int32_t vl2_kv_page_gather(const void* kpool, const void* vpool, void* k16, void* v16, const int32_t* table_row, int32_t nkv, int32_t smax,
+                           int32_t n_pages, int32_t p0, int32_t p1, void* stream);
 /* greedy argmax (first maximal index) of fp32 logits -> *tok (device int32) and hist[step] if hist != NULL.
  * state != NULL (device int32[2] = {position, step}): hist index = state[1], then both counters advance by one, so the
  * whole decode step is replayable from a hipGraph.  HF:generation/utils.py _sample with do_sample=False. */

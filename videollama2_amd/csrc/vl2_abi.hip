@@ -41,6 +41,7 @@ static constexpr bool kLab = false;
 #include "k_attn_shared.h"
 #include "k_kv8.h"
 #include "k_attn_paged.h"
+#include "k_attn_paged_shared.h"
 
 static thread_local char g_err[512] = "";
 static int32_t fail(int32_t code, const char* fmt, ...) {
@@ -1294,6 +1295,65 @@ extern "C" int32_t vl2_kv_page_scatter(const void* k16, const void* v16, void* k
     hipLaunchKernelGGL(kv_page_scatter_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, ST(stream), (const bf16_t*)k16, (const bf16_t*)v16,
                        (bf16_t*)kpool, (bf16_t*)vpool, (const int*)table_row, nkv, smax, n_pages, p0, p1);
     return launched("vl2_kv_page_scatter");
+}
+// ---- shared prefix held once in the page pool (k_attn_paged_shared.h): vl2_attn_decode_shared's three launches through page lookups, and the
+// copy of a sequence's pages back into contiguous caches
+extern "C" int32_t vl2_attn_decode_shared_paged(const void* qkv, void* kpool, void* vpool, const int32_t* page_table, const int32_t* prefix_pages,
+                                                const float* cos_t, const float* sin_t, float* partial, int64_t partial_floats, void* out, int32_t B,
+                                                int64_t qkv_bs, int32_t table_bs, int32_t n_pages, int64_t out_bs, int32_t nh, int32_t nkv, int32_t P,
+                                                int32_t own_cap, int32_t rope_rows, const int32_t* pos_dev, float scale, void* stream) {
+    if (!qkv || !kpool || !vpool || !page_table || !prefix_pages || !cos_t || !sin_t || !partial || !out || !pos_dev)
+        return fail(VL2_E_BADARG, "vl2_attn_decode_shared_paged: null pointer");
+    if (nh <= 0 || nkv <= 0 || B <= 0) return fail(VL2_E_BADARG, "vl2_attn_decode_shared_paged: need nh, nkv, B > 0 (got %d, %d, %d)", nh, nkv, B);
+    if (nh % nkv) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: need nh = nkv*group");
+    if (n_pages < 1) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: n_pages %d: the pool holds at least the parking page", n_pages);
+    if (P <= 0 || P % 64) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: P %d must be a positive multiple of 64 (whole pages are shared)", P);
+    if (own_cap <= 0 || own_cap % 64) return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: own_cap %d must be a positive multiple of 64", own_cap);
+    if (table_bs <= 0 || (int64_t)P / 64 + own_cap / 64 > table_bs)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: %d prefix pages + %d own pages outside a table row of %d pages", P / 64, own_cap / 64,
+                    table_bs);
+    if ((int64_t)P + own_cap > rope_rows)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: positions up to %lld outside the cos/sin tables (%d rows)", (long long)P + own_cap - 1,
+                    rope_rows);
+    if (qkv_bs < ((int64_t)nh + 2 * nkv) * 128 || (qkv_bs & 7) || out_bs < (int64_t)nh * 128 || !ALIGNED16(qkv) || !ALIGNED16(kpool) || !ALIGNED16(vpool))
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: rows must hold their heads' 128 elements, qkv rows and pools at 16-byte alignment");
+    const int64_t partial_bs = vl2_attn_decode_shared_partial_floats(P, own_cap, nh);
+    if (partial_floats < partial_bs * B)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: partial of %lld floats, need %lld", (long long)partial_floats, (long long)(partial_bs * B));
+    const int group = nh / nkv;
+    if ((int64_t)nkv * B > 65535 || ((int64_t)B * group + 127) / 128 > 65535)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_shared_paged: too many requests (%d)", B);
+    int chunk, nps;
+    attn_shared_split(P, chunk, nps);
+    const int nsplit_cap = nps + own_cap / 64;
+    const float sl2 = scale * 1.4426950408889634f;
+    SharedPrefixPagedArgs a{};
+    a.q = (const bf16_t*)qkv; a.q_rs = (long)qkv_bs; a.k = (const bf16_t*)kpool; a.v = (const bf16_t*)vpool;
+    a.smax = 0; a.P = P; a.n = B; a.nh = nh; a.nkv = nkv; a.group = group; a.chunk = chunk; a.nsplit = nps;
+    a.scale_log2e = sl2; a.ws = partial;
+    a.pos_dev = pos_dev; a.cos_t = cos_t; a.sin_t = sin_t; a.own_cap = own_cap; a.nsplit_cap = nsplit_cap; a.partial_bs = (long)partial_bs;
+    a.prefix_pages = (const int*)prefix_pages; a.n_pages = n_pages;
+    hipLaunchKernelGGL(attn_prefix_paged_kernel, dim3(nps, nkv, (B * group + 127) / 128), dim3(256), 0, ST(stream), a);
+    hipLaunchKernelGGL(attn_decode_own_paged_kernel, dim3(own_cap / 64, nkv * B, (group + 3) / 4), dim3(256), 0, ST(stream), (const bf16_t*)qkv,
+                       (bf16_t*)kpool, (bf16_t*)vpool, (const int*)page_table, cos_t, sin_t, partial, nh, group, nkv, own_cap, P, nps, nsplit_cap,
+                       n_pages, table_bs, pos_dev, sl2, (long)qkv_bs, (long)partial_bs);
+    hipLaunchKernelGGL(attn_shared_combine_kernel, dim3(nh, B), dim3(128), 0, ST(stream), (const float*)partial, (bf16_t*)out, P, nps, own_cap,
+                       nsplit_cap, pos_dev, (long)partial_bs, (long)out_bs);
+    return launched("vl2_attn_decode_shared_paged");
+}
+extern "C" int32_t vl2_kv_page_gather(const void* kpool, const void* vpool, void* k16, void* v16, const int32_t* table_row, int32_t nkv, int32_t smax,
+                                      int32_t n_pages, int32_t p0, int32_t p1, void* stream) {
+    if (!k16 || !v16 || !kpool || !vpool || !table_row) return fail(VL2_E_BADARG, "vl2_kv_page_gather: null pointer");
+    if (nkv <= 0 || smax <= 0) return fail(VL2_E_BADARG, "vl2_kv_page_gather: need nkv, smax > 0 (got %d, %d)", nkv, smax);
+    if (n_pages < 1) return fail(VL2_E_SHAPE, "vl2_kv_page_gather: n_pages %d: the pool holds at least the parking page", n_pages);
+    if (p0 < 0 || p0 > p1 || p1 > smax) return fail(VL2_E_SHAPE, "vl2_kv_page_gather: rows [%d, %d) outside the cache (%d)", p0, p1, smax);
+    if (!ALIGNED16(k16) || !ALIGNED16(v16) || !ALIGNED16(kpool) || !ALIGNED16(vpool))
+        return fail(VL2_E_SHAPE, "vl2_kv_page_gather: need 16-byte aligned caches and pools");
+    if (p0 == p1) return 0;
+    const long nrows = 2L * nkv * (p1 - p0);
+    hipLaunchKernelGGL(kv_page_gather_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, ST(stream), (const bf16_t*)kpool, (const bf16_t*)vpool,
+                       (bf16_t*)k16, (bf16_t*)v16, (const int*)table_row, nkv, smax, n_pages, p0, p1);
+    return launched("vl2_kv_page_gather");
 }
 extern "C" int32_t vl2_argmax(const float* logits, int32_t V, int32_t* tok, int32_t* hist, int32_t step, int32_t* state,
                               void* stream) {

@@ -821,19 +821,21 @@ class HipMistralDecoder(nn.Module):
                 ops.argmax(bb["logits"][b], bb["tok"][b:b + 1])
         self._decode_kernels_batched(nb, bb, attend)
 
-    def capture_batch_graph(self, nb, sampled=False):
+    def capture_batch_graph(self, nb, sampled=False, attend=None, mode=()):
         """{the draws + the whole batched decode step} as ONE hipGraph per (batch size, sampled) (tokens, positions and the
         draw settings live on the device, so the same graph replays for every step).  sampled=False: one argmax launch per
         request; sampled=True: one ops.sample_tokens launch for all nb rows, whatever mix of greedy and sampled slots they hold.
-        enable_fp8_decode / enable_mxfp4_decode (on / off) drop them all (_invalidate_graphs): the next step captures the weights then selected."""
+        enable_fp8_decode / enable_mxfp4_decode (on / off) drop them all (_invalidate_graphs): the next step captures the weights then selected.
+        attend / mode: the step's attention callable when it is not the slots' own, and what the key names it by (the resident prefix of a
+        ContinuousBatcher: `_paged_prefix_attend`, ("prefix", shared rows))."""
         graphs = self.__dict__.setdefault("_batch_graphs", {})
-        key = (nb, bool(sampled))
+        key = (nb, bool(sampled)) + tuple(mode)
         if key in graphs:
             return graphs[key]
         if self.tp > 1:
             raise NotImplementedError("hipGraph decode is built for the single-GPU decoder (collectives are launched eagerly)")
         bb = self._bb
-        step = lambda: self._batched_step(nb, sampled)
+        step = lambda: self._batched_step(nb, sampled, None, attend)
         graphs[key] = g = self._capture(step, step, (bb["tok"], bb["pos"], bb["logits"], bb["sstep"]))
         return g
 
@@ -967,8 +969,9 @@ class HipMistralDecoder(nn.Module):
         return (res, torch.stack(all_logits)) if return_logits else res
 
     # ------------------------------------------------------------------ batched decode over a shared prompt prefix
-    def _shared_prefix_refusals(self):
-        if getattr(self, "_paged_kv", False):
+    def _shared_prefix_refusals(self, paged_ok=False):
+        """paged_ok: the caller keeps the prefix and the own rows in pages (the resident prefix of a ContinuousBatcher)."""
+        if not paged_ok and getattr(self, "_paged_kv", False):
             raise NotImplementedError("shared-prefix decode: the paged KV cache is on (the private caches of this mode are contiguous): call "
                                       "enable_paged_kv(0, False) first")
         if self._fp8_kv:
@@ -1062,6 +1065,30 @@ class HipMistralDecoder(nn.Module):
             graph = self._capture(step, step, (sp["tok"], sp["pos"], sp["logits"], sp["sstep"]))
         return self._batched_loop(sp, nb, max_new_tokens, eos, return_logits, graph, sampled, lambda: self._decode_kernels_batched(nb, sp, attend))
 
+    # ------------------------------------------------------------------ a shared prefix held once in the page pool
+    def _paged_prefix_attend(self, px, nb):
+        """The attention callable of a step over a resident prefix: prefix phase + own rows + combine through the page table (one
+        ops.attn_decode_shared_paged call per layer).  px: the batcher's handle (serving.PrefixHandle: shared_rows, own_cap, prefix_pages on
+        the device, partial)."""
+        bb = self._bb
+
+        def attend(li, qkv, o):
+            ops.attn_decode_shared_paged(qkv, bb["kpool"][li], bb["vpool"][li], bb["table"], px.prefix_pages, bb["cos_t"], bb["sin_t"],
+                                         px.partial, o, self.nh, self.nkv, px.shared_rows, px.own_cap, bb["pos"][:nb], self.hd ** -0.5)
+        return attend
+
+    def _prefix_rows_to_pages(self, slot, p0, p1):
+        """Rows [p0, p1) of the single-sequence cache -> the pages slot's table row names, every layer."""
+        bb = self._bb
+        for li in range(self.n_layers):
+            ops.kv_page_scatter(self.kcache[li], self.vcache[li], bb["kpool"][li], bb["vpool"][li], bb["table"][slot], p0, p1)
+
+    def _prefix_rows_from_pages(self, slot, p0, p1):
+        """The inverse: rows [p0, p1) of the single-sequence cache <- the pages slot's table row names, every layer."""
+        bb = self._bb
+        for li in range(self.n_layers):
+            ops.kv_page_gather(bb["kpool"][li], bb["vpool"][li], self.kcache[li], self.vcache[li], bb["table"][slot], p0, p1)
+
 
 HipQwen2Decoder = HipMistralDecoder      # same decoder; the q/k/v bias is picked up from the state dict (weights.pack_decoder)
 
@@ -1111,7 +1138,7 @@ class HipMixtralDecoder(HipMistralDecoder):
             self._shared_prefix_refusals()
         raise NotImplementedError("MoE (mixtral) decoder: batched decoding not built")
 
-    def _shared_prefix_refusals(self):
+    def _shared_prefix_refusals(self, paged_ok=False):
         raise NotImplementedError("MoE (mixtral) decoder: shared-prefix decode is not built (its batched decoding is not)")
 
     def _ensure_batch(self, B, owner=None):

@@ -756,6 +756,73 @@ def attn_decode_shared(qkv, kprefix, vprefix, kown, vown, cos_t, sin_t, partial,
     return out
 
 
+def kv_page_gather(kpool, vpool, kcache, vcache, table_row, p0, p1):
+    """include/vl2hip.h vl2_kv_page_gather, the inverse of `kv_page_scatter`: rows [p0, p1) of the pages a table row names (int32
+    [>= ceil(smax / 64)], contiguous) -> one sequence's contiguous 16-bit caches [nkv, smax, 128], byte for byte; rows whose page id is outside
+    the pools are skipped and nothing else in the caches is written."""
+    e = _lib.elem_dtype()
+    _dtypes("kv_page_gather", (kcache, e, "kcache"), (vcache, e, "vcache"), (table_row, torch.int32, "table_row"))
+    n_pages, nkv = _chk_pools("kv_page_gather", kpool, vpool)
+    if kcache.dim() != 3 or kcache.shape[0] != nkv or kcache.shape[2] != 128 or vcache.shape != kcache.shape or \
+            not (kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError(f"kv_page_gather: need contiguous 16-bit caches [nkv = {nkv}, smax, 128], got {tuple(kcache.shape)}, {tuple(vcache.shape)}")
+    smax = kcache.shape[1]
+    if table_row.dim() != 1 or not table_row.is_contiguous() or table_row.numel() < (smax + KV_PAGE_ROWS - 1) // KV_PAGE_ROWS:
+        raise ValueError(f"kv_page_gather: the table row must be a contiguous int32 vector of at least {(smax + KV_PAGE_ROWS - 1) // KV_PAGE_ROWS} "
+                         f"entries, got {tuple(table_row.shape)}")
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 <= p1 <= smax:
+        raise ValueError(f"kv_page_gather: rows [{p0}, {p1}) outside the cache ({smax})")
+    for t, name in ((kcache, "kcache"), (vcache, "vcache"), (kpool, "kpool"), (vpool, "vpool"), (table_row, "table_row")):
+        _chk(t, t.dtype, name)
+    _lib.call("vl2_kv_page_gather", _p(kpool), _p(vpool), _p(kcache), _p(vcache), _p(table_row), nkv, smax, n_pages, p0, p1, _stream())
+
+
+def attn_decode_shared_paged(qkv, kpool, vpool, table, prefix_pages, cos_t, sin_t, partial, out, nh, nkv, P, own_cap, pos_dev, scale):
+    """include/vl2hip.h vl2_attn_decode_shared_paged: `attn_decode_shared` with the shared prefix and the own rows in pages of one pool.  P (a
+    positive multiple of 64) shared positions live in the pages prefix_pages (int32 [>= P / 64], contiguous) for every request; request b's own
+    rows from position P on live in the pages table[b, P / 64 + s], s < own_cap / 64 (own_cap a multiple of 64).  qkv [B, (nh+2nkv)*128]
+    un-roped, pools [n_pages, nkv, 64, 128], table int32 [>= B, >= P / 64 + own_cap / 64], pos_dev int32 [B] absolute positions, out
+    [B, nh*128]; partial: at least B * shared_partial_floats(P, own_cap, nh) floats.  Bit for bit `attn_decode_shared` on contiguous copies of
+    the same rows.  Everything is checked here, before the library is called."""
+    P, own_cap = int(P), int(own_cap)
+    if qkv.dim() != 2 or nh <= 0 or nkv <= 0 or nh % nkv or qkv.shape[1] != (nh + 2 * nkv) * 128:
+        raise ValueError(f"attn_decode_shared_paged: qkv must be [B, (nh + 2 nkv) * 128] with nh = nkv * group, got {tuple(qkv.shape)} for nh {nh}, "
+                         f"nkv {nkv}")
+    B = qkv.shape[0]
+    e = _lib.elem_dtype()
+    operands = ((qkv, e, "qkv"), (out, e, "out"), (cos_t, torch.float32, "cos_t"), (sin_t, torch.float32, "sin_t"),
+                (partial, torch.float32, "partial"), (pos_dev, torch.int32, "pos_dev"), (table, torch.int32, "table"),
+                (prefix_pages, torch.int32, "prefix_pages"))
+    _dtypes("attn_decode_shared_paged", *operands)
+    n_pages, _ = _chk_pools("attn_decode_shared_paged", kpool, vpool, nkv)
+    if P <= 0 or P % KV_PAGE_ROWS:
+        raise ValueError(f"attn_decode_shared_paged: P {P} must be a positive multiple of 64 (whole pages are shared)")
+    if own_cap <= 0 or own_cap % KV_PAGE_ROWS:
+        raise ValueError(f"attn_decode_shared_paged: own_cap {own_cap} must be a positive multiple of 64")
+    if table.dim() != 2 or table.shape[0] < B or table.stride(1) != 1 or table.shape[1] < (P + own_cap) // KV_PAGE_ROWS:
+        raise ValueError(f"attn_decode_shared_paged: the page table must be int32 [>= {B}, >= {(P + own_cap) // KV_PAGE_ROWS}] ({P // KV_PAGE_ROWS} "
+                         f"prefix + {own_cap // KV_PAGE_ROWS} own pages), got {tuple(table.shape)}")
+    if prefix_pages.dim() != 1 or not prefix_pages.is_contiguous() or prefix_pages.numel() < P // KV_PAGE_ROWS:
+        raise ValueError(f"attn_decode_shared_paged: prefix_pages must be a contiguous int32 vector of at least {P // KV_PAGE_ROWS} entries, got "
+                         f"{tuple(prefix_pages.shape)}")
+    if cos_t.shape != sin_t.shape or cos_t.dim() != 2 or cos_t.shape[1] != 64 or cos_t.shape[0] < P + own_cap or \
+            not (cos_t.is_contiguous() and sin_t.is_contiguous()):
+        raise ValueError(f"attn_decode_shared_paged: positions up to {P + own_cap - 1} need contiguous cos / sin tables [>= {P + own_cap}, 64], got "
+                         f"{tuple(cos_t.shape)}")
+    if pos_dev.numel() < B or out.dim() != 2 or out.shape[0] < B or out.shape[1] != nh * 128:
+        raise ValueError(f"attn_decode_shared_paged: need {B} positions and out [B, nh * 128], got {pos_dev.numel()}, {tuple(out.shape)}")
+    need = B * shared_partial_floats(P, own_cap, nh)
+    if partial.numel() < need:
+        raise ValueError(f"attn_decode_shared_paged: partial holds {partial.numel()} floats, need {need}")
+    for t, dt, name in operands + ((kpool, e, "kpool"), (vpool, e, "vpool")):
+        _chk(t, dt, name)
+    _lib.call("vl2_attn_decode_shared_paged", _p(qkv), _p(kpool), _p(vpool), _p(table), _p(prefix_pages), _p(cos_t), _p(sin_t), _p(partial),
+              partial.numel(), _p(out), B, qkv.stride(0), table.stride(0), n_pages, out.stride(0), nh, nkv, P, own_cap, cos_t.shape[0],
+              _p(pos_dev), float(scale), _stream())
+    return out
+
+
 def argmax(logits, tok, hist=None, step=0, state=None):
     _lib.call("vl2_argmax", _p(logits), logits.numel(), _p(tok), _p(hist), step, _p(state), _stream())
 

@@ -4,7 +4,10 @@ CPU tests call it without a decoder.
 
 A page is 64 consecutive positions of one sequence (all kv heads, every layer, K and V: one id names them all).  Page 0 is the PARKING page:
 it is never handed out, and the table row of a slot that holds no request points its entry 0 at it, so that a step computed for such a slot
-at position 0 reads and writes finite, harmless rows."""
+at position 0 reads and writes finite, harmless rows.
+
+A resident prefix (kernels: csrc/k_attn_paged_shared.h) shares the WHOLE pages of a prompt prefix among the requests of a
+batcher: `shared_rows`, a request's own reservation `own_pages_needed` and the row of an empty slot behind the prefix, `prefix_parked_row`."""
 
 PAGE_ROWS = 64
 PARKING_PAGE = 0
@@ -27,6 +30,24 @@ def table_row(pages, pages_per_seq):
 def parked_row(pages_per_seq):
     """The row of a slot that holds no request: entry 0 = the parking page, the rest not assigned."""
     return table_row([PARKING_PAGE], pages_per_seq)
+
+
+def shared_rows(P):
+    """Rows of a P-row prefix that a resident prefix shares: its WHOLE pages, 64 * floor(P / 64).  The ragged tail
+    P - shared_rows(P) (0 .. 63 rows) is prepended to every request's suffix."""
+    return int(P) // PAGE_ROWS * PAGE_ROWS
+
+
+def own_pages_needed(P, n, max_new, max_seq_len):
+    """Pages a request of n suffix rows behind a resident prefix of P rows reserves for itself: every page of its P + n prompt rows and its
+    new tokens that is not one of the prefix's whole pages."""
+    return pages_needed(int(P) + int(n), max_new, max_seq_len) - int(P) // PAGE_ROWS
+
+
+def prefix_parked_row(prefix_pages, pages_per_seq):
+    """The row of a slot that holds no request while a prefix is resident: the prefix pages, then the parking page, then not assigned -- a
+    step computed for such a slot at position shared_rows(P) reads the prefix and reads and writes row 0 of page 0."""
+    return table_row(list(prefix_pages) + [PARKING_PAGE], pages_per_seq)
 
 
 class PagePool:

@@ -17,8 +17,9 @@ import itertools
 
 import torch
 
+from . import _lib
 from .decoder import eos_set
-from .paging import admit_fifo, pages_needed, parked_row, table_row
+from .paging import PAGE_ROWS, admit_fifo, own_pages_needed, pages_needed, parked_row, prefix_parked_row, shared_rows, table_row
 
 
 class _Request:
@@ -29,6 +30,16 @@ class _Request:
         self.sampler, self.u = sampler, u              # (temperature, top_k, top_p) and the request's uniform numbers, or None: greedy
         self.tokens, self.slot, self.done = [], None, False
         self.need, self.pages = 0, None                # paged KV: the reservation (pages) and, once admitted, the page ids
+
+
+class PrefixHandle:
+    """A resident prefix of a ContinuousBatcher (`open_prefix`): P prompt rows of which the first `shared_rows` = 64 * floor(P / 64) live
+    once in the page pool, in `pages`; the ragged tail rows are kept here and prepended to every request's suffix."""
+    __slots__ = ("P", "shared_rows", "pages", "tail", "open", "epoch", "own_cap", "prefix_pages", "partial", "ids")
+
+    def __init__(self, P, pages, tail):
+        self.P, self.shared_rows, self.pages, self.tail = P, shared_rows(P), list(pages), tail
+        self.open, self.epoch, self.ids = True, None, None
 
 
 class ContinuousBatcher:
@@ -46,7 +57,13 @@ class ContinuousBatcher:
     the WHOLE reservation (`paging.admit_fifo`): the head of the queue joins only when a slot is free and the pool holds all its pages,
     otherwise nobody is admitted in that step -- so no request can run out of pages in flight and the step's graph replays untouched (it reads
     the page table from the device).  A request's tokens are bit for bit the contiguous slots'.  A request that can never fit the pool is
-    refused at `submit`.  Not built: growing a reservation page by page, preemption.  The decoder refuses the switch with requests in flight."""
+    refused at `submit`.  Not built: growing a reservation page by page, preemption.  The decoder refuses the switch with requests in flight.
+    resident prefix (`open_prefix(x_prefix)` under the paged KV cache): many questions about one video arriving over time.
+    The whole pages of the prefix are held ONCE in the pool and appear under the same ids in every request's table row; a request reserves
+    only its own pages, and the step reads the prefix once for all requests (`ops.attn_decode_shared_paged`).  While it is open every
+    `submit` names it (`prefix=handle`); a request's tokens are bit for bit its solo
+    `generate_batch([cat(x_prefix[Pf:], suffix)], shared_prefix=x_prefix[:Pf])` on an unpaged decoder, Pf = the shared rows.  One prefix at a
+    time; `close_prefix()` returns its pages."""
 
     def __init__(self, decoder, max_slots=4, eos_token_id=None, use_graph=None):
         if decoder.tp > 1:
@@ -61,23 +78,108 @@ class ContinuousBatcher:
         self._ids = itertools.count()
         self.steps = 0
         self.bb = decoder._ensure_batch(self.max_slots, owner=self)
+        self._prefix = None                     # the resident prefix (PrefixHandle), or None
+
+    # ---- the resident prefix
+    @torch.no_grad()
+    def open_prefix(self, x_prefix):
+        """Make x_prefix [P, D] (the spliced rows every coming request begins with) resident: prefill its shared rows Pf = 64 * floor(P / 64)
+        once, keep them in Pf / 64 pages of the pool for as long as the prefix is open, and point every slot's table row at them.  Returns
+        the handle `submit(..., prefix=handle)` takes (`.P`, `.shared_rows`, `.pages`).  Refused before any kernel call: a decoder the
+        shared-prefix mode refuses (tensor parallelism, head_dim != 128, fp8 prefill, Mixtral), no paged KV cache, requests waiting or in
+        flight, a prefix already open, fewer than 64 rows, a prefix that leaves no room for a suffix row, a pool too small."""
+        from .ops import shared_partial_floats
+        dec = self.dec
+        self._open_prefix_refusals()
+        P = int(x_prefix.shape[0])
+        Pf = shared_rows(P)
+        if Pf < PAGE_ROWS:
+            raise ValueError(f"open_prefix: a prefix of {P} rows has no whole page of {PAGE_ROWS} rows to share")
+        if P + 1 > dec.max_seq_len:
+            raise ValueError(f"open_prefix: a prefix of {P} rows leaves no room for a suffix row in the KV cache ({dec.max_seq_len})")
+        bb = dec._ensure_batch(self.max_slots, owner=self)
+        self.bb = bb                            # (nothing is in flight: buffers reallocated since the last step lose nobody's rows)
+        n_pre, smallest = Pf // PAGE_ROWS, own_pages_needed(P, 1, 1, dec.max_seq_len)
+        if n_pre + smallest > bb["pool"].n_free:
+            raise ValueError(f"open_prefix: the prefix needs {n_pre} pages and one request at least {smallest} more, the pool has "
+                             f"{bb['pool'].n_free} free (of {bb['pool'].n_pages - 1}; enable_paged_kv(n_pages))")
+        pps = bb["pages_per_seq"]
+        x_prefix = x_prefix.to(device=dec._dev)
+        h = PrefixHandle(P, bb["pool"].alloc(n_pre), x_prefix[Pf:].clone())
+        try:
+            dec.prefill(x_prefix[:Pf])                              # into the single-sequence cache: what every request's extend reads
+            dec._set_table_rows(0, [prefix_parked_row(h.pages, pps)] * self.max_slots)
+            dec._prefix_rows_to_pages(0, 0, Pf)
+            h.epoch = dec.cache_epoch
+            h.own_cap = PAGE_ROWS * (pps - n_pre)
+            h.prefix_pages = torch.tensor(h.pages, dtype=torch.int32).to(dec._dev)
+            h.partial = torch.empty((self.max_slots * shared_partial_floats(Pf, h.own_cap, dec.nh),), dtype=torch.float32, device=dec._dev)
+        except BaseException:
+            bb["pool"].free(h.pages)
+            dec._set_table_rows(0, [parked_row(pps)] * self.max_slots)
+            raise
+        self._drop_prefix_graphs()
+        self._prefix = h
+        return h
+
+    def _open_prefix_refusals(self):
+        """The refusals of open_prefix that do not depend on the prefix (ModelBatcher.open_video makes them before the encoder runs)."""
+        dec = self.dec
+        dec._shared_prefix_refusals(paged_ok=True)       # everything the shared-prefix mode refuses, except paging itself
+        if not dec.paged_kv:
+            raise RuntimeError("open_prefix: the resident prefix lives in the page pool: call decoder.enable_paged_kv(n_pages) first")
+        if self.in_flight():
+            raise RuntimeError(f"open_prefix: {self.in_flight()} requests are waiting or in flight: drain them (run()) first")
+        if self._prefix is not None:
+            raise RuntimeError("open_prefix: a prefix is open already (one resident prefix per batcher): close_prefix() first")
+
+    def close_prefix(self):
+        """Give the prefix pages back and park every slot on page 0 again.  Refused with requests waiting or in flight."""
+        h = self._prefix
+        if h is None:
+            raise RuntimeError("close_prefix: no prefix is open")
+        if self.in_flight():
+            raise RuntimeError(f"close_prefix: {self.in_flight()} requests are waiting or in flight: drain them (run()) first")
+        h.open, self._prefix = False, None
+        self._drop_prefix_graphs()
+        if self.dec._bb is self.bb:             # (reallocated buffers took the pool and the table with them)
+            self.bb["pool"].free(h.pages)
+            self.dec._set_table_rows(0, [parked_row(self.bb["pages_per_seq"])] * self.max_slots)
+
+    def _drop_prefix_graphs(self):
+        graphs = self.dec.__dict__.get("_batch_graphs", {})
+        for key in [k for k in graphs if "prefix" in k]:
+            del graphs[key]
 
     # ---- admission
     def submit(self, inputs_embeds, max_new_tokens=2048, streamer=None, stopping_criteria=None, do_sample=False, temperature=None, top_k=None,
-               top_p=None, generator=None, **warpers):
+               top_p=None, generator=None, prefix=None, **warpers):
         """Queue one request (inputs_embeds [S, D]: the spliced prompt of `prepare_inputs_labels_for_multimodal`).  It is prefilled
         and joins the batch at the next `step()` with a free slot.  Returns the request id.
         do_sample=True: HF `_sample` with the warpers temperature -> top_k -> top_p, HF's defaults (1.0, 50, 1.0) for the unspecified ones and
         HF's checks, as `VideoLLaMA2Hip.generate(do_sample=True)`; other warpers (`repetition_penalty`, ...) are refused unless neutral.  The
         request's uniform numbers are drawn here from `generator` (or torch's generator for the device), as many and in the same call as a solo
-        `HipMistralDecoder.generate(sampler=...)` of this request draws them, so it samples the same tokens under the same seed."""
+        `HipMistralDecoder.generate(sampler=...)` of this request draws them, so it samples the same tokens under the same seed.
+        prefix=handle (`open_prefix`): inputs_embeds holds only the request's own n >= 1 rows; its prompt is the prefix's P rows and then
+        these, and it reserves only the pages behind the prefix's whole pages.  While a prefix is open every request names it."""
         from .model import UNBUILT_WARPERS, resolve_sampler
+        h = self._prefix
+        if prefix is not h:
+            if prefix is None:
+                raise ValueError("submit: a prefix is open on this batcher: pass prefix=handle (plain and prefix requests do not share a step), "
+                                 "or close_prefix() first")
+            raise ValueError("submit: the prefix handle is closed or was opened on another batcher" if isinstance(prefix, PrefixHandle)
+                             else f"submit: prefix must be the handle open_prefix returned, got {type(prefix).__name__}")
         unknown = set(warpers) - {k for k, _ in UNBUILT_WARPERS}
         if unknown:
             raise TypeError(f"submit() got unexpected keyword arguments {sorted(unknown)}")
         given = dict(temperature=temperature, top_k=top_k, top_p=top_p, **warpers)
         sampler = resolve_sampler(dict({k: v for k, v in given.items() if v is not None}, do_sample=do_sample, generator=generator))
         S = inputs_embeds.shape[0]
+        if h is not None:                # the prompt is prefix ++ suffix
+            if S < 1:
+                raise ValueError("submit: a request behind a prefix needs at least one row of its own")
+            S += h.P
         if S > self.dec.max_seq_len:
             raise ValueError(f"sequence length {S} exceeds the KV cache ({self.dec.max_seq_len})")
         crit = stopping_criteria
@@ -85,7 +187,14 @@ class ContinuousBatcher:
             crit = [crit]
         max_new = min(int(max_new_tokens), self.dec.max_seq_len - S + 1)
         need = 0
-        if self.dec.paged_kv:            # its whole reservation; one that the pool can never hold would block the queue for ever
+        if h is not None:                # its own pages only; the pool it can ever draw on excludes the prefix pages
+            need = own_pages_needed(h.P, S - h.P, max_new, self.dec.max_seq_len)
+            if need > self.dec._n_pages - 1 - len(h.pages):
+                raise ValueError(f"paged KV cache: the request needs {need} pages of its own ({h.P} prefix rows + {S - h.P} rows + {max_new} new "
+                                 f"tokens), the pool serves {self.dec._n_pages - 1 - len(h.pages)} beside the prefix's {len(h.pages)} "
+                                 f"(enable_paged_kv(n_pages); page 0 is the parking page)")
+            inputs_embeds = torch.cat([h.tail, inputs_embeds.to(device=h.tail.device, dtype=h.tail.dtype)])   # the rows its extend computes
+        elif self.dec.paged_kv:          # its whole reservation; one that the pool can never hold would block the queue for ever
             need = pages_needed(S, max_new, self.dec.max_seq_len)
             if need > self.dec._n_pages - 1:
                 raise ValueError(f"paged KV cache: the request needs {need} pages ({S} prompt rows + {max_new} new tokens), the pool serves "
@@ -102,6 +211,7 @@ class ContinuousBatcher:
     def _admit(self):
         bb, dec = self.bb, self.dec
         paged = dec.paged_kv
+        h = self._prefix
         if paged:                # strict FIFO on whole reservations: how many requests from the head of the queue join in this step
             free = sum(r is None for r in self.slots)
             take = admit_fifo([r.need for r in self.waiting], free, bb["pool"].n_free)
@@ -114,9 +224,20 @@ class ContinuousBatcher:
             if paged:            # its pages into the slot's table row (one small H2D copy; the rest of the row is -1), before its prefill's rows go there
                 take -= 1
                 r.pages = bb["pool"].alloc(r.need)
-                dec._set_table_rows(slot, [table_row(r.pages, bb["pages_per_seq"])])
-            dec.prefill_slot(slot, r.x, bb["logits"][slot])                       # rows [0, S) of the slot's cache (fp8 KV: quantised from the staging cache)
-            bb["pos"][slot:slot + 1].fill_(r.x.shape[0])
+                dec._set_table_rows(slot, [table_row((h.pages if h is not None else []) + r.pages, bb["pages_per_seq"])])
+            if h is not None:    # tail ++ suffix on top of the shared rows of the single-sequence cache, then its rows into the own pages
+                Pf = h.shared_rows
+                if dec.cache_epoch != h.epoch:           # someone else used the single-sequence cache: its rows [0, Pf) come back from the pages
+                    dec._prefix_rows_from_pages(slot, 0, Pf)
+                dec.pos = Pf
+                dec.extend(r.x, start_pos=Pf, logits_out=bb["logits"][slot])
+                dec._prefix_rows_to_pages(slot, Pf, Pf + r.x.shape[0])
+                dec.pos = Pf
+                h.epoch = dec.cache_epoch
+                bb["pos"][slot:slot + 1].fill_(Pf + r.x.shape[0])
+            else:
+                dec.prefill_slot(slot, r.x, bb["logits"][slot])                   # rows [0, S) of the slot's cache (fp8 KV: quantised from the staging cache)
+                bb["pos"][slot:slot + 1].fill_(r.x.shape[0])
             T, k, p = r.sampler if r.sampler is not None else (0.0, 0, 1.0)                # temperature 0: a greedy slot
             bb["samp_T"][slot:slot + 1].fill_(T); bb["samp_k"][slot:slot + 1].fill_(k); bb["samp_p"][slot:slot + 1].fill_(p)
             bb["sstep"][slot:slot + 1].zero_()
@@ -132,6 +253,10 @@ class ContinuousBatcher:
         self.dec._ensure_batch(self.max_slots, owner=self)     # raises if ANOTHER batcher owns the slots with requests in flight
         self.dec._bb_busy = self                               # from here on generate_batch / a second batcher are refused while we hold requests
         if self.dec._bb is not self.bb:       # the slot buffers (and caches) were reallocated: a larger generate_batch() on this decoder, enable_fp8_kv
+            if self._prefix is not None:      # its pages went with the pool
+                self._prefix.open, self._prefix = False, None
+                raise RuntimeError("the decoder's batch buffers were reallocated while a prefix was open: its pages are gone; open_prefix() "
+                                   "again and resubmit")
             if any(r is not None for r in self.slots):
                 raise RuntimeError("the decoder's batch buffers were reallocated while requests were in flight: use one batcher per decoder "
                                    "and do not call generate_batch() with more sequences than max_slots on it")
@@ -143,15 +268,17 @@ class ContinuousBatcher:
         bb, dec = self.bb, self.dec
         nb = occupied[-1] + 1
         holes = [s for s in range(nb) if self.slots[s] is None]
+        h = self._prefix
         if holes:            # an empty slot below the highest occupied one still computes (and is ignored): park it at position 0, greedy
             idx = torch.tensor(holes, device=bb["pos"].device)
-            bb["pos"][idx] = 0
+            bb["pos"][idx] = 0 if h is None else h.shared_rows     # a resident prefix: behind its shared rows, on row 0 of the parking page
             bb["samp_T"][idx] = 0.0
         sampled = any(self.slots[s].sampler is not None for s in occupied)
+        attend, mode = (None, ()) if h is None else (dec._paged_prefix_attend(h, nb), ("prefix", h.shared_rows))
         if self.use_graph:
-            dec.capture_batch_graph(nb, sampled).replay()     # the draws of every slot's logits + the forward of the new tokens
+            dec.capture_batch_graph(nb, sampled, attend, mode).replay()     # the draws of every slot's logits + the forward of the new tokens
         else:
-            dec._batched_step(nb, sampled)
+            dec._batched_step(nb, sampled, None, attend)
         self.steps += 1
         toks = bb["tok"][:nb].tolist()                    # one small D2H per step for the stop checks (as HF's loop does)
         out = {}
@@ -180,7 +307,8 @@ class ContinuousBatcher:
         if r.pages is not None:          # paged KV: the pages go back to the pool (dirty: whoever gets them overwrites what it reads) and the
             self.bb["pool"].free(r.pages)            # slot's row points at the parking page again
             r.pages = None
-            self.dec._set_table_rows(slot, [parked_row(self.bb["pages_per_seq"])])
+            pps, h = self.bb["pages_per_seq"], self._prefix
+            self.dec._set_table_rows(slot, [parked_row(pps) if h is None else prefix_parked_row(h.pages, pps)])
 
     def in_flight(self):
         return sum(r is not None for r in self.slots) + len(self.waiting)
@@ -201,15 +329,59 @@ class ModelBatcher:
         self.inner = ContinuousBatcher(model.decoder, max_slots, eos_token_id, use_graph)
 
     @torch.no_grad()
-    def submit(self, input_ids, images=None, attention_mask=None, **kw):
+    def open_video(self, input_ids_prefix, images):
+        """One video, many questions arriving over time: input_ids_prefix (the token ids every question begins with, modal sentinels
+        included) and its media are encoded ONCE, spliced as `generate_shared` splices its common prefix, and made resident
+        (`ContinuousBatcher.open_prefix`).  Returns the handle `submit(input_ids, prefix=handle)` takes."""
+        from .model import MODAL_INDEX_MAP
+        self.inner._open_prefix_refusals()                   # before the encoder or any other kernel runs
+        ids_l = (input_ids_prefix[0] if input_ids_prefix.dim() == 2 else input_ids_prefix).tolist()
+        n_sent = sum(1 for t in ids_l if t in set(MODAL_INDEX_MAP.values()))
+        media = list(images) if images is not None else []
+        if n_sent != len(media):
+            raise ValueError(f"open_video: the prefix holds {n_sent} modal sentinels for {len(media)} media")
+        feats = []
+        if n_sent:
+            f = self.model.encode_images_or_videos(media)
+            feats = [f[k] for k in range(n_sent)]
+        h = self.inner.open_prefix(self.model._embed_suffix(ids_l, feats, 0))
+        h.ids = ids_l
+        return h
+
+    def close_video(self):
+        self.inner.close_prefix()
+
+    def _embed_behind(self, h, input_ids, images):
+        """The embedding rows of a question behind the resident prefix h: its ids must begin with the prefix's and bring no media of their own."""
+        from .model import MODAL_INDEX_MAP
+        if not isinstance(h, PrefixHandle) or h.ids is None:
+            raise ValueError("submit: prefix must be the handle open_video returned")
+        if h is not self.inner._prefix:
+            raise ValueError("submit: the prefix handle is closed or was opened on another batcher")
+        ids_l = (input_ids[0] if input_ids.dim() == 2 else input_ids).tolist()
+        t = len(h.ids)
+        if ids_l[:t] != h.ids or len(ids_l) <= t:
+            raise ValueError(f"submit: the request's ids must begin with the open prefix's {t} ids and add at least one of their own")
+        if images is not None or any(tok in set(MODAL_INDEX_MAP.values()) for tok in ids_l[t:]):
+            raise ValueError("submit: a request behind an open prefix brings no media of its own (a modal sentinel follows the prefix's ids, or "
+                             "images were passed)")
+        emb = torch.empty((len(ids_l) - t, self.model.decoder.D), dtype=_lib.elem_dtype(), device=self.model._dev)
+        self.model._embed_ids(torch.tensor(ids_l[t:], dtype=torch.int64).to(self.model._dev), emb)
+        return emb
+
+    @torch.no_grad()
+    def submit(self, input_ids, images=None, attention_mask=None, prefix=None, **kw):
         """Queue one request; the keywords are ContinuousBatcher.submit's, and unspecified sampling settings come from the model's
-        generation_config as in `VideoLLaMA2Hip.generate(do_sample=True)`."""
+        generation_config as in `VideoLLaMA2Hip.generate(do_sample=True)`.  prefix=handle (`open_video`): input_ids begin with the
+        prefix's ids; only the rest is embedded, and the video is not encoded again."""
         from .model import UNBUILT_WARPERS, resolve_sampler
         sampler = resolve_sampler(kw, getattr(self.model, "generation_config", None))
         for k in ("do_sample", "temperature", "top_k", "top_p", "generator") + tuple(k for k, _ in UNBUILT_WARPERS):
             kw.pop(k, None)
         if sampler is not None:
             kw.update(do_sample=True, temperature=sampler[0], top_k=sampler[1], top_p=sampler[2], generator=sampler[3])
+        if prefix is not None:
+            return self.inner.submit(self._embed_behind(prefix, input_ids, images), prefix=prefix, **kw)
         ids = input_ids if input_ids.dim() == 2 else input_ids[None]
         emb, lens = self.model._inputs_embeds(ids, attention_mask, images)
         return self.inner.submit(emb[0, :lens[0]], **kw)
