@@ -419,6 +419,23 @@ int32_t vl2_attn_decode_shared_paged(const void* qkv, void* kpool, void* vpool, 
                                      int32_t own_cap, int32_t rope_rows, const int32_t* pos_dev, float scale, void* stream);
 int32_t vl2_kv_page_gather(const void* kpool, const void* vpool, void* k16, void* v16, const int32_t* table_row, int32_t nkv, int32_t smax,
                            int32_t n_pages, int32_t p0, int32_t p1, void* stream);
+/* ---- the paged KV cache in fp8 (csrc/k_attn_paged_kv8.h; additions of ABI 7; head_dim 128; OPTIONAL): the pages above holding the rows of the
+ * fp8 KV cache.  Per layer FOUR pools under one page id: k8pool / v8pool = uint8 [n_pages, nkv, 64, 128] e4m3fn codes, kspool / vspool = fp32
+ * [n_pages, nkv, 64] power-of-two row scales (the format of vl2_kv_quant).  page_table, the parking page and seq_cap as vl2_attn_decode_paged.
+ * vl2_attn_decode_kv8_paged: vl2_attn_decode_kv8_batched with the codes and scales of a 64-key slice read from (and the new token's quantised
+ *   rows appended to) the page the table names for it: the same grid, partial layout [B][nh][ceil(ctx_cap/64)][130], arithmetic and combine --
+ *   bit for bit that call on contiguous copies of the same codes and scales.  A sequence writes NOTHING if pos_dev[b] >= seq_cap; a 64-key
+ *   slice whose page id is outside [0, n_pages) touches none of the four pools (nor appends).  In both cases the sequence's output row is
+ *   unspecified: the host discards it.
+ * vl2_kv_page_quant: rows [p0, p1) (p0 == p1: nothing) of ONE sequence's contiguous 16-bit caches k16 / v16 [nkv, smax, 128] -> codes and scales
+ *   in the pages named by its table row (table_row: ceil(smax / 64) entries), K and V in one launch: byte for byte what vl2_kv_quant writes at
+ *   those rows of a contiguous fp8 cache; rows whose page id is outside [0, n_pages) are skipped and nothing else in the pools is written. */
+int32_t vl2_attn_decode_kv8_paged(const void* qkv, void* k8pool, void* v8pool, float* kspool, float* vspool, const int32_t* page_table,
+                                  const float* cos_t, const float* sin_t, float* partial, void* out, int32_t B, int64_t qkv_bs, int32_t table_bs,
+                                  int32_t n_pages, int64_t out_bs, int32_t nh, int32_t nkv, int32_t seq_cap, const int32_t* pos_dev, int32_t ctx_cap,
+                                  float scale, void* stream);
+int32_t vl2_kv_page_quant(const void* k16, const void* v16, void* k8pool, void* v8pool, float* kspool, float* vspool, const int32_t* table_row,
+                          int32_t nkv, int32_t smax, int32_t n_pages, int32_t p0, int32_t p1, void* stream);
 /* greedy argmax (first maximal index) of fp32 logits -> *tok (device int32) and hist[step] if hist != NULL.
  * state != NULL (device int32[2] = {position, step}): hist index = state[1], then both counters advance by one, so the
  * whole decode step is replayable from a hipGraph.  HF:generation/utils.py _sample with do_sample=False. */

@@ -42,6 +42,7 @@ static constexpr bool kLab = false;
 #include "k_kv8.h"
 #include "k_attn_paged.h"
 #include "k_attn_paged_shared.h"
+#include "k_attn_paged_kv8.h"
 
 static thread_local char g_err[512] = "";
 static int32_t fail(int32_t code, const char* fmt, ...) {
@@ -1354,6 +1355,47 @@ extern "C" int32_t vl2_kv_page_gather(const void* kpool, const void* vpool, void
     hipLaunchKernelGGL(kv_page_gather_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, ST(stream), (const bf16_t*)kpool, (const bf16_t*)vpool,
                        (bf16_t*)k16, (bf16_t*)v16, (const int*)table_row, nkv, smax, n_pages, p0, p1);
     return launched("vl2_kv_page_gather");
+}
+// ---- paged KV cache in fp8 (k_attn_paged_kv8.h): vl2_attn_decode_paged and vl2_kv_page_scatter on pools of e4m3 codes and row scales
+extern "C" int32_t vl2_attn_decode_kv8_paged(const void* qkv, void* k8pool, void* v8pool, float* kspool, float* vspool, const int32_t* page_table,
+                                             const float* cos_t, const float* sin_t, float* partial, void* out, int32_t B, int64_t qkv_bs,
+                                             int32_t table_bs, int32_t n_pages, int64_t out_bs, int32_t nh, int32_t nkv, int32_t seq_cap,
+                                             const int32_t* pos_dev, int32_t ctx_cap, float scale, void* stream) {
+    if (!qkv || !k8pool || !v8pool || !kspool || !vspool || !page_table || !cos_t || !sin_t || !partial || !out || !pos_dev)
+        return fail(VL2_E_BADARG, "vl2_attn_decode_kv8_paged: null pointer");
+    if (nh <= 0 || nkv <= 0 || B <= 0) return fail(VL2_E_BADARG, "vl2_attn_decode_kv8_paged: need nh, nkv, B > 0 (got %d, %d, %d)", nh, nkv, B);
+    if (nh % nkv) return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: need nh = nkv*group");
+    if (n_pages < 1) return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: n_pages %d: the pool holds at least the parking page", n_pages);
+    if (seq_cap <= 0 || seq_cap % 64) return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: seq_cap %d must be a positive multiple of 64", seq_cap);
+    if (table_bs <= 0 || seq_cap > 64 * (int64_t)table_bs)
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: seq_cap %d outside a table row of %d pages", seq_cap, table_bs);
+    if (ctx_cap <= 0 || ctx_cap > seq_cap) return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: ctx_cap %d outside seq_cap (%d)", ctx_cap, seq_cap);
+    if (!ALIGNED16(qkv) || !ALIGNED16(k8pool) || !ALIGNED16(v8pool) || (qkv_bs & 7))
+        return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: need 16-byte aligned qkv rows and pools");
+    if ((int64_t)nkv * B > 65535) return fail(VL2_E_SHAPE, "vl2_attn_decode_kv8_paged: too many sequences (%d)", B);
+    const int group = nh / nkv;
+    const int nsplit = (ctx_cap + 63) / 64;
+    const long partial_bs = (long)nh * nsplit * 130;
+    hipLaunchKernelGGL(attn_decode_kv8_paged_kernel, dim3(nsplit, nkv * B, (group + 3) / 4), dim3(256), 0, ST(stream), (const bf16_t*)qkv,
+                       (uint8_t*)k8pool, (uint8_t*)v8pool, kspool, vspool, (const int*)page_table, cos_t, sin_t, partial, nh, group, nkv, seq_cap,
+                       n_pages, table_bs, pos_dev, scale * 1.4426950408889634f, (long)qkv_bs, partial_bs);
+    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(nh, B), dim3(128), 0, ST(stream), partial, (bf16_t*)out, nsplit, 0, pos_dev,
+                       partial_bs, (long)out_bs);
+    return launched("vl2_attn_decode_kv8_paged");
+}
+extern "C" int32_t vl2_kv_page_quant(const void* k16, const void* v16, void* k8pool, void* v8pool, float* kspool, float* vspool,
+                                     const int32_t* table_row, int32_t nkv, int32_t smax, int32_t n_pages, int32_t p0, int32_t p1, void* stream) {
+    if (!k16 || !v16 || !k8pool || !v8pool || !kspool || !vspool || !table_row) return fail(VL2_E_BADARG, "vl2_kv_page_quant: null pointer");
+    if (nkv <= 0 || smax <= 0) return fail(VL2_E_BADARG, "vl2_kv_page_quant: need nkv, smax > 0 (got %d, %d)", nkv, smax);
+    if (n_pages < 1) return fail(VL2_E_SHAPE, "vl2_kv_page_quant: n_pages %d: the pool holds at least the parking page", n_pages);
+    if (p0 < 0 || p0 > p1 || p1 > smax) return fail(VL2_E_SHAPE, "vl2_kv_page_quant: rows [%d, %d) outside the cache (%d)", p0, p1, smax);
+    if (!ALIGNED16(k16) || !ALIGNED16(v16) || !ALIGNED16(k8pool) || !ALIGNED16(v8pool))
+        return fail(VL2_E_SHAPE, "vl2_kv_page_quant: need 16-byte aligned caches and pools");
+    if (p0 == p1) return 0;
+    const long nrows = 2L * nkv * (p1 - p0);
+    hipLaunchKernelGGL(kv_page_quant_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, ST(stream), (const bf16_t*)k16, (const bf16_t*)v16,
+                       (uint8_t*)k8pool, (uint8_t*)v8pool, kspool, vspool, (const int*)table_row, nkv, smax, n_pages, p0, p1);
+    return launched("vl2_kv_page_quant");
 }
 extern "C" int32_t vl2_argmax(const float* logits, int32_t V, int32_t* tok, int32_t* hist, int32_t step, int32_t* state,
                               void* stream) {

@@ -178,6 +178,7 @@ class HipMistralDecoder(nn.Module):
         self.decode_fp8 = self.prefill_fp8 = self.decode_mxfp4 = False
         self._fp8_kv, self.kv8 = False, None        # enable_fp8_kv: per layer (k8, v8, ks, vs), the single-sequence fp8 KV cache
         self._paged_kv, self._n_pages = False, 0    # enable_paged_kv: the batched paths keep their slots' rows in pages of a shared pool
+        self._paged_fp8 = False                     # enable_paged_kv(fp8=True): those pages hold fp8 rows (codes + row scales)
 
     def _rope_tables(self, rows):
         """cos / sin of pos * inv_freq for positions 0 .. rows-1, fp32 [rows, head_dim / 2] on the device."""
@@ -271,6 +272,8 @@ class HipMistralDecoder(nn.Module):
         arithmetic and never the default: with it off every path keeps its bits; tests/fp8kv_oracle.py defines the format."""
         if on:
             self._fp8_kv_refusals()
+        # (whatever its pages hold: fp8 pages are entered through enable_paged_kv(fp8=True) alone.  Under fp8 pages the words "16-bit rows" are
+        # not true; the message is kept word for word because tests/test_paged_kv_host.py and tests/test_paged_prefix_host.py pin it)
         if on and getattr(self, "_paged_kv", False):
             raise NotImplementedError("fp8 KV cache: the paged KV cache is on (its pages hold 16-bit rows): call enable_paged_kv(0, False) first")
         busy = getattr(self, "_bb_busy", None)
@@ -299,8 +302,16 @@ class HipMistralDecoder(nn.Module):
         """Whether the batched paths keep their slots' KV rows in pages of a shared pool (enable_paged_kv)."""
         return self._paged_kv
 
+    @property
+    def paged_kv_fp8(self):
+        """Whether the pages of the paged KV cache hold fp8 rows (enable_paged_kv(n_pages, fp8=True))."""
+        return self._paged_kv and self._paged_fp8
+
     def kv_page_bytes(self):
-        """Bytes of ONE page over all layers, K and V: n_layers * 2 * nkv * 64 * 128 * 2 (8.39 MB at 7B; 64 pages = a 4096-row slot)."""
+        """Bytes of ONE page over all layers, K and V: n_layers * 2 * nkv * 64 * 128 * 2 (8.39 MB at 7B; 64 pages = a 4096-row slot); while
+        fp8 pages are on, n_layers * 2 * nkv * 64 * (128 + 4): a code per element and a scale per row (4.33 MB at 7B)."""
+        if self.paged_kv_fp8:
+            return self.n_layers * 2 * self.nkv * ops.KV_PAGE_ROWS * (128 + 4)
         return self.n_layers * 2 * self.nkv * ops.KV_PAGE_ROWS * 128 * 2
 
     def _paged_kv_refusals(self):
@@ -313,7 +324,7 @@ class HipMistralDecoder(nn.Module):
             raise NotImplementedError("paged KV cache: the fp8 KV cache is on (the pages hold 16-bit rows): call enable_fp8_kv(False) first")
 
     @torch.no_grad()
-    def enable_paged_kv(self, n_pages, on=True):
+    def enable_paged_kv(self, n_pages, on=True, fp8=False):
         """OPTIONAL layout, never the default: the batched paths (`generate_batch`, ContinuousBatcher) keep their slots' 16-bit KV rows in
         PAGES of 64 positions drawn from one pool of `n_pages` pages per layer (csrc/k_attn_paged.h) instead of a
         private cache of max_seq_len rows per slot: a request holds ceil(min(S + max_new, max_seq_len) / 64) pages, `kv_page_bytes()` each,
@@ -323,7 +334,14 @@ class HipMistralDecoder(nn.Module):
         into its pages.  Switching drops every captured batch graph and the slot buffers; it is refused while a batcher holds requests in
         flight.  The single-sequence paths (`generate`, `extend`, the prefix cache) keep their contiguous cache and are untouched.
         Tensor parallelism, head_dim != 128, Mixtral, the fp8 KV cache (each switch refuses the other) and
-        `generate_batch(shared_prefix=...)` raise NotImplementedError.  Not built: growing a reservation page by page, preemption."""
+        `generate_batch(shared_prefix=...)` raise NotImplementedError.  Not built: growing a reservation page by page, preemption.
+        fp8=True (csrc/k_attn_paged_kv8.h): the pages hold the rows of the fp8 KV cache -- e4m3fn codes and one
+        power-of-two scale per (kv head, row), `enable_fp8_kv`'s format -- so a page is `kv_page_bytes()` = 0.52 x the 16-bit page and every
+        batched result is bit for bit that of contiguous fp8-KV slots (a decoder with `enable_fp8_kv()`): the staging rows are quantised into
+        the pages, the step appends and reads codes and scales.  It is the only way into the combination: `fp8_kv` stays off (the
+        single-sequence cache is never paged and keeps its 16-bit bits), the two switches still refuse each other, and a resident prefix
+        (`ContinuousBatcher.open_prefix`) is refused on fp8 pages.  Switching the page format drops the slot buffers and the graphs like
+        any other call."""
         if on:
             self._paged_kv_refusals()
             if int(n_pages) < 2:
@@ -333,6 +351,7 @@ class HipMistralDecoder(nn.Module):
             raise RuntimeError("enable_paged_kv: a ContinuousBatcher holds requests in flight on this decoder's slots, whose rows would change "
                                "layout under them: drain it (run()) first")
         self._paged_kv, self._n_pages = bool(on), int(n_pages) if on else 0
+        self._paged_fp8 = bool(on and fp8)
         self._invalidate_graphs()
         self._bb = None                              # the slots are in the other layout: the next batched call allocates them again
         return self
@@ -725,10 +744,14 @@ class HipMistralDecoder(nn.Module):
         elif self._paged_kv:     # the pools, the page table (every slot parked on page 0), the allocator + one sequence's 16-bit staging cache;
             self._paged_kv_refusals()                # no tensor of max_seq_len rows per slot
             pps = (smax + ops.KV_PAGE_ROWS - 1) // ops.KV_PAGE_ROWS
-            pools = [ops.kv_pool_alloc(self._n_pages, self.nkv, self._dev) for _ in range(self.n_layers)]
+            if self._paged_fp8:  # fp8 pages: per layer (k8pool, v8pool, kspool, vspool), codes 0 and scales 1 (the parking page stays finite)
+                pools = dict(pools8=[ops.kv8_pool_alloc(self._n_pages, self.nkv, self._dev) for _ in range(self.n_layers)])
+            else:
+                pools = [ops.kv_pool_alloc(self._n_pages, self.nkv, self._dev) for _ in range(self.n_layers)]
+                pools = dict(kpool=[p[0] for p in pools], vpool=[p[1] for p in pools])
             # the table covers 64 * pps >= max_seq_len positions and the kernel wants cos / sin rows for all of them
             cos_t, sin_t = (self.cos_t, self.sin_t) if pps * ops.KV_PAGE_ROWS == smax else self._rope_tables(pps * ops.KV_PAGE_ROWS)
-            caches = dict(kpool=[p[0] for p in pools], vpool=[p[1] for p in pools], pool=PagePool(self._n_pages), pages_per_seq=pps,
+            caches = dict(**pools, pool=PagePool(self._n_pages), pages_per_seq=pps,
                           table=torch.tensor([parked_row(pps)] * B, dtype=torch.int32).to(self._dev), cos_t=cos_t, sin_t=sin_t,
                           stage=([torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)],
                                  [torch.zeros((self.nkv, smax, self.hd), **bf) for _ in range(self.n_layers)]))
@@ -744,8 +767,8 @@ class HipMistralDecoder(nn.Module):
     def prefill_slot(self, slot, x, logits_out):
         """Prefill one request (inputs_embeds x [S, D]) into batch slot `slot`: rows [0, S) of its caches, the last row's fp32 logits in
         logits_out.  fp8 KV: through the 16-bit staging cache, whose rows [0, S) are then quantised into the slot.  Paged KV: through the
-        staging cache likewise, its rows then copied into the pages the slot's table row names (assigned by the caller beforehand).  The
-        decoder's own single-sequence position is left alone."""
+        staging cache likewise, its rows then copied (fp8 pages: quantised) into the pages the slot's table row names (assigned by the caller
+        beforehand).  The decoder's own single-sequence position is left alone."""
         bb, own_pos = self._bb, self.pos
         if self._fp8_kv:
             self.prefill(x, cache=bb["stage"], logits_out=logits_out)
@@ -753,6 +776,9 @@ class HipMistralDecoder(nn.Module):
         elif self._paged_kv:     # through the 16-bit staging cache (the prefill keeps its bits), then its rows [0, S) into the slot's pages
             self.prefill(x, cache=bb["stage"], logits_out=logits_out)
             for li in range(self.n_layers):
+                if self._paged_fp8:                  # (fp8 pages: quantised on their way into the pages)
+                    ops.kv_page_quant(bb["stage"][0][li], bb["stage"][1][li], bb["pools8"][li], bb["table"][slot], 0, x.shape[0])
+                    continue
                 ops.kv_page_scatter(bb["stage"][0][li], bb["stage"][1][li], bb["kpool"][li], bb["vpool"][li], bb["table"][slot], 0, x.shape[0])
         else:
             self.prefill(x, cache=([k[slot] for k in bb["k"]], [v[slot] for v in bb["v"]]), logits_out=logits_out)
@@ -775,7 +801,8 @@ class HipMistralDecoder(nn.Module):
         With enable_fp8_kv the attention of every form above runs on the slots' fp8 caches (one vl2_attn_decode_kv8_batched launch per layer):
         a row's attention is bit for bit the single-sequence fp8-KV step's.
         With enable_paged_kv the attention of every form above reads and appends the slots' rows in their pages (one vl2_attn_decode_paged
-        launch per layer, the page table read from the device): bit for bit the contiguous slots' step.
+        launch per layer, the page table read from the device): bit for bit the contiguous slots' step.  On fp8 pages
+        (enable_paged_kv(fp8=True)) that launch is vl2_attn_decode_kv8_paged: bit for bit the contiguous fp8-KV slots' step.
         bb / attend: the step's buffers and its attention callable attend(li, qkv, o) when they are not the slots' (the shared-prefix mode,
         `_shared_attend`)."""
         bb = self._bb if bb is None else bb
@@ -797,6 +824,9 @@ class HipMistralDecoder(nn.Module):
             if self._fp8_kv:
                 return ops.attn_decode_kv8_batched(qkv, tuple(t[:nb] for t in bb["kv8"][li]), self.cos_t, self.sin_t, bb["partial"], o,
                                                    self.nh, self.nkv, bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
+            if self._paged_kv and self._paged_fp8:
+                return ops.attn_decode_kv8_paged(qkv, bb["pools8"][li], bb["table"], bb["cos_t"], bb["sin_t"], bb["partial"], o, self.nh, self.nkv,
+                                                 bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
             if self._paged_kv:
                 return ops.attn_decode_paged(qkv, bb["kpool"][li], bb["vpool"][li], bb["table"], bb["cos_t"], bb["sin_t"], bb["partial"], o,
                                              self.nh, self.nkv, bb["pos"][:nb], self.max_seq_len, self.hd ** -0.5)
@@ -1126,7 +1156,7 @@ class HipMixtralDecoder(HipMistralDecoder):
         raise NotImplementedError("MoE (mixtral) decoder: the fp8 KV cache is not built for it (its step runs the MoE GEMVs on the 16-bit "
                                   "cache): keep the 16-bit cache")
 
-    def enable_paged_kv(self, n_pages, on=True):
+    def enable_paged_kv(self, n_pages, on=True, fp8=False):
         raise NotImplementedError("MoE (mixtral) decoder: the paged KV cache is not built for it (its batched decoding is not): keep the "
                                   "contiguous cache")
 

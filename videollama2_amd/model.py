@@ -426,12 +426,13 @@ class VideoLLaMA2Hip(nn.Module):
         self._prefix_rec = None                      # the resident rows a prefix-cache call recorded are gone
         return self
 
-    def enable_paged_kv(self, n_pages, on=True):
+    def enable_paged_kv(self, n_pages, on=True, fp8=False):
         """OPTIONAL layout, never the default: the batched paths (`generate_batch`, the padded-batch `generate`, `batcher()`) keep their slots'
         KV rows in pages of 64 positions from one pool of n_pages pages (`HipMistralDecoder.enable_paged_kv`): slot memory
         follows the requests' lengths, not max_seq_len, and every result keeps its bits.  The single-sequence `generate` and its prefix cache are
-        untouched.  Tensor-parallel decoders, Mixtral, head_dim != 128, the fp8 KV cache and generate_shared refuse it."""
-        self.decoder.enable_paged_kv(n_pages, on)
+        untouched.  Tensor-parallel decoders, Mixtral, head_dim != 128, the fp8 KV cache and generate_shared refuse it.  fp8=True: the pages
+        hold fp8 rows, 0.52 x the bytes, and every batched result is bit for bit the contiguous fp8-KV slots'."""
+        self.decoder.enable_paged_kv(n_pages, on, fp8=fp8)
         return self
 
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None):

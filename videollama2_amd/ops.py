@@ -672,6 +672,91 @@ def attn_decode_paged(qkv, kpool, vpool, table, cos_t, sin_t, partial, out, nh, 
     return out
 
 
+def kv8_pool_alloc(n_pages, nkv, device):
+    """One layer's fp8 page pools (include/vl2hip.h, csrc/k_attn_paged_kv8.h) as (k8pool, v8pool, kspool, vspool): e4m3fn codes uint8
+    [n_pages, nkv, 64, 128], zero, and fp32 row scales [n_pages, nkv, 64], one (page 0, the parking page, must dequantise to finite rows)."""
+    n_pages = int(n_pages)
+    if n_pages < 1 or nkv <= 0:
+        raise ValueError(f"kv8_pool_alloc: need n_pages >= 1 (the parking page) and nkv > 0, got {n_pages}, {nkv}")
+    codes = lambda: torch.zeros((n_pages, nkv, KV_PAGE_ROWS, 128), dtype=torch.uint8, device=device)
+    scales = lambda: torch.ones((n_pages, nkv, KV_PAGE_ROWS), dtype=torch.float32, device=device)
+    return codes(), codes(), scales(), scales()
+
+
+def _chk_pools8(who, pools8, nkv=None):
+    k8pool, v8pool, kspool, vspool = pools8
+    _dtypes(who, (k8pool, torch.uint8, "k8pool"), (v8pool, torch.uint8, "v8pool"), (kspool, torch.float32, "kspool"), (vspool, torch.float32, "vspool"))
+    if k8pool.dim() != 4 or tuple(k8pool.shape[2:]) != (KV_PAGE_ROWS, 128) or v8pool.shape != k8pool.shape or kspool.shape != k8pool.shape[:3] or \
+            vspool.shape != kspool.shape or (nkv is not None and k8pool.shape[1] != nkv):
+        raise ValueError(f"{who}: the pools must be codes [n_pages, nkv, 64, 128] and scales [n_pages, nkv, 64], got {tuple(k8pool.shape)}, "
+                         f"{tuple(v8pool.shape)}, {tuple(kspool.shape)}, {tuple(vspool.shape)}")
+    if not all(t.is_contiguous() for t in pools8):
+        raise ValueError(f"{who}: the pools' pages must be contiguous")
+    return k8pool.shape[0], k8pool.shape[1]
+
+
+def kv_page_quant(kcache, vcache, pools8, table_row, p0, p1):
+    """include/vl2hip.h vl2_kv_page_quant: rows [p0, p1) of one sequence's contiguous 16-bit caches [nkv, smax, 128] -> e4m3fn codes and
+    power-of-two row scales in the pages its table row names (int32 [>= ceil(smax / 64)], contiguous) of pools8 = (k8pool, v8pool, kspool,
+    vspool): byte for byte what `kv_quant` writes at those rows of a contiguous fp8 cache; rows whose page id is outside the pools are skipped."""
+    e = _lib.elem_dtype()
+    _dtypes("kv_page_quant", (kcache, e, "kcache"), (vcache, e, "vcache"), (table_row, torch.int32, "table_row"))
+    n_pages, nkv = _chk_pools8("kv_page_quant", pools8)
+    if kcache.dim() != 3 or kcache.shape[0] != nkv or kcache.shape[2] != 128 or vcache.shape != kcache.shape or \
+            not (kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError(f"kv_page_quant: need contiguous 16-bit caches [nkv = {nkv}, smax, 128], got {tuple(kcache.shape)}, {tuple(vcache.shape)}")
+    smax = kcache.shape[1]
+    if table_row.dim() != 1 or not table_row.is_contiguous() or table_row.numel() < (smax + KV_PAGE_ROWS - 1) // KV_PAGE_ROWS:
+        raise ValueError(f"kv_page_quant: the table row must be a contiguous int32 vector of at least {(smax + KV_PAGE_ROWS - 1) // KV_PAGE_ROWS} "
+                         f"entries, got {tuple(table_row.shape)}")
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 <= p1 <= smax:
+        raise ValueError(f"kv_page_quant: rows [{p0}, {p1}) outside the cache ({smax})")
+    k8pool, v8pool, kspool, vspool = pools8
+    for t, name in ((kcache, "kcache"), (vcache, "vcache"), (k8pool, "k8pool"), (v8pool, "v8pool"), (kspool, "kspool"), (vspool, "vspool"),
+                    (table_row, "table_row")):
+        _chk(t, t.dtype, name)
+    _lib.call("vl2_kv_page_quant", _p(kcache), _p(vcache), _p(k8pool), _p(v8pool), _p(kspool), _p(vspool), _p(table_row), nkv, smax, n_pages,
+              p0, p1, _stream())
+
+
+def attn_decode_kv8_paged(qkv, pools8, table, cos_t, sin_t, partial, out, nh, nkv, pos_dev, ctx_cap, scale):
+    """include/vl2hip.h vl2_attn_decode_kv8_paged: `attn_decode_kv8_batched` on the paged fp8 cache.  qkv [B, (nh+2nkv)*128] un-roped, pools8 =
+    (k8pool, v8pool, kspool, vspool): codes uint8 [n_pages, nkv, 64, 128] and scales fp32 [n_pages, nkv, 64]; table, out, pos_dev, seq_cap,
+    cos_t / sin_t and partial as `attn_decode_paged`.  Bit for bit `attn_decode_kv8_batched` on contiguous copies of the same codes and scales.
+    Everything is checked here, before the library is called."""
+    if qkv.dim() != 2 or nh <= 0 or nkv <= 0 or nh % nkv or qkv.shape[1] != (nh + 2 * nkv) * 128:
+        raise ValueError(f"attn_decode_kv8_paged: qkv must be [B, (nh + 2 nkv) * 128] with nh = nkv * group, got {tuple(qkv.shape)} for nh {nh}, "
+                         f"nkv {nkv}")
+    B = qkv.shape[0]
+    e = _lib.elem_dtype()
+    operands = ((qkv, e, "qkv"), (out, e, "out"), (cos_t, torch.float32, "cos_t"), (sin_t, torch.float32, "sin_t"),
+                (partial, torch.float32, "partial"), (pos_dev, torch.int32, "pos_dev"), (table, torch.int32, "table"))
+    _dtypes("attn_decode_kv8_paged", *operands)
+    n_pages, _ = _chk_pools8("attn_decode_kv8_paged", pools8, nkv)
+    if table.dim() != 2 or table.shape[0] < B or table.shape[1] < 1 or table.stride(1) != 1:
+        raise ValueError(f"attn_decode_kv8_paged: the page table must be int32 [>= {B}, pages_per_seq], got {tuple(table.shape)}")
+    seq_cap = table.shape[1] * KV_PAGE_ROWS
+    ctx_cap = int(ctx_cap)
+    if not 0 < ctx_cap <= seq_cap:
+        raise ValueError(f"attn_decode_kv8_paged: ctx_cap {ctx_cap} outside the table's {seq_cap} positions")
+    if cos_t.shape != sin_t.shape or cos_t.dim() != 2 or cos_t.shape[1] != 64 or cos_t.shape[0] < seq_cap or not (cos_t.is_contiguous() and sin_t.is_contiguous()):
+        raise ValueError(f"attn_decode_kv8_paged: positions up to {seq_cap - 1} need contiguous cos / sin tables [>= {seq_cap}, 64], got "
+                         f"{tuple(cos_t.shape)}")
+    if pos_dev.numel() < B or out.dim() != 2 or out.shape[0] < B or out.shape[1] != nh * 128:
+        raise ValueError(f"attn_decode_kv8_paged: need {B} positions and out [B, nh * 128], got {pos_dev.numel()}, {tuple(out.shape)}")
+    need = B * nh * ((ctx_cap + 63) // 64) * 130
+    if partial.numel() < need:
+        raise ValueError(f"attn_decode_kv8_paged: partial holds {partial.numel()} floats, need {need}")
+    k8pool, v8pool, kspool, vspool = pools8
+    for t, dt, name in operands + ((k8pool, torch.uint8, "k8pool"), (v8pool, torch.uint8, "v8pool"), (kspool, torch.float32, "kspool"),
+                                   (vspool, torch.float32, "vspool")):
+        _chk(t, dt, name)
+    _lib.call("vl2_attn_decode_kv8_paged", _p(qkv), _p(k8pool), _p(v8pool), _p(kspool), _p(vspool), _p(table), _p(cos_t), _p(sin_t), _p(partial),
+              _p(out), B, qkv.stride(0), table.stride(0), n_pages, out.stride(0), nh, nkv, seq_cap, _p(pos_dev), ctx_cap, float(scale), _stream())
+    return out
+
+
 _APPEND_WS = {}
 
 

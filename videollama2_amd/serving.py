@@ -58,6 +58,9 @@ class ContinuousBatcher:
     otherwise nobody is admitted in that step -- so no request can run out of pages in flight and the step's graph replays untouched (it reads
     the page table from the device).  A request's tokens are bit for bit the contiguous slots'.  A request that can never fit the pool is
     refused at `submit`.  Not built: growing a reservation page by page, preemption.  The decoder refuses the switch with requests in flight.
+    fp8 pages (decoder.enable_paged_kv(n_pages, fp8=True)): the same reservations, admission and retirement on pages of
+    fp8 rows; a request is prefilled into the staging cache and quantised into its pages, and its tokens are bit for bit those of the
+    contiguous fp8-KV slots.  A resident prefix is refused on them.
     resident prefix (`open_prefix(x_prefix)` under the paged KV cache): many questions about one video arriving over time.
     The whole pages of the prefix are held ONCE in the pool and appear under the same ids in every request's table row; a request reserves
     only its own pages, and the step reads the prefix once for all requests (`ops.attn_decode_shared_paged`).  While it is open every
@@ -86,7 +89,7 @@ class ContinuousBatcher:
         """Make x_prefix [P, D] (the spliced rows every coming request begins with) resident: prefill its shared rows Pf = 64 * floor(P / 64)
         once, keep them in Pf / 64 pages of the pool for as long as the prefix is open, and point every slot's table row at them.  Returns
         the handle `submit(..., prefix=handle)` takes (`.P`, `.shared_rows`, `.pages`).  Refused before any kernel call: a decoder the
-        shared-prefix mode refuses (tensor parallelism, head_dim != 128, fp8 prefill, Mixtral), no paged KV cache, requests waiting or in
+        shared-prefix mode refuses (tensor parallelism, head_dim != 128, fp8 prefill, Mixtral), no paged KV cache, fp8 pages, requests waiting or in
         flight, a prefix already open, fewer than 64 rows, a prefix that leaves no room for a suffix row, a pool too small."""
         from .ops import shared_partial_floats
         dec = self.dec
@@ -128,6 +131,9 @@ class ContinuousBatcher:
         dec._shared_prefix_refusals(paged_ok=True)       # everything the shared-prefix mode refuses, except paging itself
         if not dec.paged_kv:
             raise RuntimeError("open_prefix: the resident prefix lives in the page pool: call decoder.enable_paged_kv(n_pages) first")
+        if dec.paged_kv_fp8:
+            raise NotImplementedError("open_prefix: the pages hold fp8 rows and no fp8 form of the shared-prefix kernels is built (the prefix "
+                                      "phase and extend read 16-bit rows): call decoder.enable_paged_kv(n_pages) for 16-bit pages first")
         if self.in_flight():
             raise RuntimeError(f"open_prefix: {self.in_flight()} requests are waiting or in flight: drain them (run()) first")
         if self._prefix is not None:
