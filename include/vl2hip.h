@@ -603,6 +603,29 @@ int32_t vl2_moe_route_gemv(const void* x, const float* wr, int32_t D, int32_t E,
 int32_t vl2_moe_gemv(const void* W, int64_t w_stride, int32_t ldw, const void* x, const int32_t* ids, const float* wts, const void* res,
                      void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream);
 
+/* ---- batched decode of the sparse MoE block: S tokens per step (csrc/k_moe_skinny.h).  Every table stays on the device. */
+/* Route S tokens like vl2_moe_route and (when counts / offs / gather / inv are given -- all four or none) build the COMPACT tables: a row
+ * tile of 1, so offs[e + 1] - offs[e] = counts[e], offs[E] = S*k exactly, gather [S*k] has no padding, inv [S, k].  S*k <= 16384. */
+int32_t vl2_moe_route_rows(const void* x, int32_t ldx, const float* wr, int32_t S, int32_t D, int32_t E, int32_t k, float eps, int32_t* ids,
+                           float* wts, float* logits, int32_t* counts, int32_t* offs, int32_t* gather, int32_t* inv, void* stream);
+/* Bytes of fp32 partial sums vl2_moe_gemm_skinny needs: ks * S*k * N * 4 with the K split ks of vl2_gemm_skinny_* for (N, K) -- a function
+ * of N and K only, never shrunk.  -1 for a shape the call refuses. */
+int64_t vl2_moe_gemm_skinny_part_bytes(int32_t S, int32_t k, int32_t N, int32_t K);
+/* Grouped skinny-M GEMM, S <= 64 tokens, ONE launch for all experts: C[p] = epilogue(A[src(p)] W_e^T) for the S*k permuted rows p of the
+ * compact tables (expert e owns rows offs[e] .. offs[e] + counts[e] - 1; counts[e] <= S), src(p) = rowmap ? rowmap[p] : p, A [a_rows, lda],
+ * W_e = W + e * w_stride ([N, ldw]).  The weights of an expert stream once for all its rows; an expert without rows reads nothing.  A
+ * permuted row is bit for bit vl2_gemm_skinny_bf16 on that one row with W_e.  flags VL2_GEMM_SWIGLU: C [S*k, N/2] = silu(gate) * up.
+ * N % 64 == 0 (128 with SWIGLU), K % 32 == 0; part: part_bytes >= vl2_moe_gemm_skinny_part_bytes(S, k, N, K), 16-byte aligned. */
+int32_t vl2_moe_gemm_skinny(const void* A, int32_t lda, int32_t a_rows, const int32_t* rowmap, const void* W, int64_t w_stride, int32_t ldw,
+                            void* C, int32_t ldc, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t N,
+                            int32_t K, int32_t flags, void* part, int64_t part_bytes, void* stream);
+/* vl2_moe_gemv for S tokens in one launch per form, ids / wts [S, k]; a token's rows are bit for bit vl2_moe_gemv's.
+ * flags VL2_GEMM_SWIGLU: x [S, ldx] -> y [S*k, ldy] (row t*k + j = slot j of token t).  flags 0: x = the SwiGLU rows [S*k, K] (ldx == K),
+ * y [S, ldy] = res [S, ldres] + sum_j wts[t, j] * W_{ids[t, j]} x[t*k + j]. */
+int32_t vl2_moe_gemv_batched(const void* W, int64_t w_stride, int32_t ldw, const void* x, int32_t ldx, const int32_t* ids, const float* wts,
+                             const void* res, int32_t ldres, void* y, int32_t ldy, int32_t S, int32_t E, int32_t k, int32_t N, int32_t K,
+                             float eps, int32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -268,10 +268,11 @@ __global__ __launch_bounds__(256) void moe_gemv_gu_kernel(GemvArgs g, const int*
 
 // Decode down: grid = ceil(N / 4), block 256, dynamic LDS = KS * K * 2 (the k SwiGLU rows a [KS][K]).  One output row per wave:
 // the KS experts' dot products of that row are streamed together, then y[n] = bf16(res[n] + sum_j w_j dot_j) (fp32, slot order).
+// (the body takes the workgroup index and one token's pointers so that k_moe_skinny.h can run it per token of a batch)
 template <int KS>
-__global__ __launch_bounds__(256) void moe_gemv_down_kernel(const bf16_t* __restrict__ W, long long w_stride, int ldw, const bf16_t* __restrict__ a,
-                                                            const int* __restrict__ ids, const float* __restrict__ wts,
-                                                            const bf16_t* __restrict__ res, bf16_t* __restrict__ y, int N, int K) {
+__device__ __forceinline__ void moe_gemv_down_body(const bf16_t* __restrict__ W, long long w_stride, int ldw, const bf16_t* __restrict__ a,
+                                                   const int* __restrict__ ids, const float* __restrict__ wts,
+                                                   const bf16_t* __restrict__ res, bf16_t* __restrict__ y, int N, int K, int bid) {
 #pragma clang fp reassociate(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
     bf16_t* as = (bf16_t*)vl2_smem;
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(256) void moe_gemv_down_kernel(const bf16_t* __rest
         wj[s] = wts[s];
     }
     __syncthreads();
-    const int n = blockIdx.x * 4 + wave;
+    const int n = bid * 4 + wave;
     if (n >= N) return;
     float acc[KS];
 #pragma unroll
@@ -319,4 +320,11 @@ __global__ __launch_bounds__(256) void moe_gemv_down_kernel(const bf16_t* __rest
         if (res) o = bf2f(res[n]) + o;
         y[n] = f2bf(o);
     }
+}
+
+template <int KS>
+__global__ __launch_bounds__(256) void moe_gemv_down_kernel(const bf16_t* __restrict__ W, long long w_stride, int ldw, const bf16_t* __restrict__ a,
+                                                            const int* __restrict__ ids, const float* __restrict__ wts,
+                                                            const bf16_t* __restrict__ res, bf16_t* __restrict__ y, int N, int K) {
+    moe_gemv_down_body<KS>(W, w_stride, ldw, a, ids, wts, res, y, N, K, blockIdx.x);
 }

@@ -37,6 +37,7 @@ static constexpr bool kLab = false;
 #include "k_stc.h"
 #include "k_vit.h"
 #include "k_moe.h"
+#include "k_moe_skinny.h"
 #include "k_attn_append.h"
 #include "k_attn_shared.h"
 #include "k_kv8.h"
@@ -1559,6 +1560,95 @@ extern "C" int32_t vl2_moe_gemv(const void* W, int64_t w_stride, int32_t ldw, co
     if (k == 1) VL2_MOE_DOWN(1); else if (k == 2) VL2_MOE_DOWN(2); else if (k == 3) VL2_MOE_DOWN(3); else VL2_MOE_DOWN(4);
 #undef VL2_MOE_DOWN
     return launched("vl2_moe_gemv");
+}
+
+// ------------------------------------------------------------------------------------------------ batched MoE decode, k_moe_skinny.h
+extern "C" int32_t vl2_moe_route_rows(const void* x, int32_t ldx, const float* wr, int32_t S, int32_t D, int32_t E, int32_t k, float eps, int32_t* ids,
+                                      float* wts, float* logits, int32_t* counts, int32_t* offs, int32_t* gather, int32_t* inv, void* stream) {
+    if (!x || !wr || !ids || !wts || S <= 0 || D <= 0 || E <= 0 || k <= 0) return fail(VL2_E_BADARG, "vl2_moe_route_rows: null pointer or empty shape");
+    const bool tables = counts || offs || gather || inv;
+    if (tables && (!counts || !offs || !gather || !inv)) return fail(VL2_E_BADARG, "vl2_moe_route_rows: counts / offs / gather / inv come together or not at all");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E)
+        return fail(VL2_E_UNSUPP, "vl2_moe_route_rows: need E <= %d and 1 <= k <= min(E, %d) (E=%d k=%d)", MOE_MAX_E, MOE_MAX_K, E, k);
+    if ((int64_t)S * k > MOE_SCAN_MAX) return fail(VL2_E_UNSUPP, "vl2_moe_route_rows: S * k <= %d (S=%d k=%d)", MOE_SCAN_MAX, S, k);
+    if (D % 8 || ldx % 8 || ldx < D || !ALIGNED16(x) || !ALIGNED16(wr))
+        return fail(VL2_E_SHAPE, "vl2_moe_route_rows: need D%%8==0, ldx>=D and 16-byte aligned rows (D=%d ldx=%d)", D, ldx);
+    hipStream_t s = ST(stream);
+    hipLaunchKernelGGL(moe_router_kernel, dim3((S + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, ldx, wr, S, D, E, k, eps, ids, wts, (float*)nullptr, logits);
+    if (tables) hipLaunchKernelGGL(moe_scan_kernel, dim3(1), dim3(1024), 0, s, (const int*)ids, S, E, k, 1, S * k, counts, offs, gather, inv);
+    return launched("vl2_moe_route_rows");
+}
+// the K split of the grouped skinny GEMM: skinny_plan's for (N, K), never shrunk; the staged rows (mt) from S
+static int moe_skinny_plan(int S, int N, int K, SkinnyPlan& pl) { return skinny_plan(S, N, K, INT64_MAX, false, pl); }
+extern "C" int64_t vl2_moe_gemm_skinny_part_bytes(int32_t S, int32_t k, int32_t N, int32_t K) {
+    SkinnyPlan pl;
+    if (S <= 0 || S > 64 || k <= 0 || k > MOE_MAX_K || N <= 0 || K <= 0 || N % 64 || K % 32 || moe_skinny_plan(S, N, K, pl) != SKINNY_PLAN_OK) return -1;
+    return (int64_t)pl.ks * S * k * N * 4;
+}
+extern "C" int32_t vl2_moe_gemm_skinny(const void* A, int32_t lda, int32_t a_rows, const int32_t* rowmap, const void* W, int64_t w_stride, int32_t ldw,
+                                       void* C, int32_t ldc, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t N,
+                                       int32_t K, int32_t flags, void* part, int64_t part_bytes, void* stream) {
+    if (!A || !W || !C || !counts || !offs || S <= 0 || k <= 0 || E <= 0 || N <= 0 || K <= 0 || a_rows <= 0)
+        return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_skinny: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (S > 64) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: S=%d tokens, need S<=64 (vl2_moe_gemm beyond)", S);
+    const bool sw = flags & VL2_GEMM_SWIGLU;
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_skinny: flags other than VL2_GEMM_SWIGLU not built");
+    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
+    if (K % 32) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: need K%%32==0 (K=%d)", K);
+    const int R = S * k;
+    if (lda % 8 || ldw % 8 || ldc % 4 || lda < K || ldw < K || w_stride % 8 || w_stride < (int64_t)N * ldw || ldc < (sw ? N / 2 : N) ||
+        !ALIGNED16(A) || !ALIGNED16(W) || (((uintptr_t)C) & 7))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: need 16-byte aligned rows, lda%%8==0, ldw%%8==0, ldc%%4==0, lda / ldw >= K, w_stride >= N*ldw");
+    if (a_rows < (rowmap ? S : R)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: A has %d rows, need %d", a_rows, rowmap ? S : R);
+    if (!part || !ALIGNED16(part) || part_bytes <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny: needs a 16-byte aligned buffer of fp32 partial sums");
+    SkinnyPlan pl;
+    if (moe_skinny_plan(S, N, K, pl) != SKINNY_PLAN_OK) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: no K chunking for K=%d", K);
+    const int64_t need = (int64_t)pl.ks * R * N * 4;
+    if (need > part_bytes)
+        return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny: partial buffer too small (%lld bytes, need %lld: the K split is never shrunk)", (long long)part_bytes, (long long)need);
+    MoeSkinnyArgs q{};
+    q.g = SkinnyArgs{(const bf16_t*)A, (const bf16_t*)W, (float*)part, S, N, K, lda, ldw, pl.kslice, pl.kchunk};
+    q.counts = counts; q.offs = offs; q.rowmap = rowmap; q.w_stride = w_stride; q.R = R; q.a_rows = a_rows;
+    hipStream_t s = ST(stream);
+    const dim3 gk(N / 64, pl.ks, E), b(256);
+    if (pl.mt == 1) { lds_attr<moe_skinny_kernel<1>>(65536); hipLaunchKernelGGL(moe_skinny_kernel<1>, gk, b, pl.lds, s, q); }
+    else if (pl.mt == 2) { lds_attr<moe_skinny_kernel<2>>(65536); hipLaunchKernelGGL(moe_skinny_kernel<2>, gk, b, pl.lds, s, q); }
+    else { lds_attr<moe_skinny_kernel<4>>(65536); hipLaunchKernelGGL(moe_skinny_kernel<4>, gk, b, pl.lds, s, q); }
+    SkinnyReduceArgs r{(const float*)part, C, nullptr, nullptr, R, R, N, pl.ks, ldc, 0, nullptr};
+    const dim3 g((R * ((sw ? N / 2 : N) / 4) + 255) / 256);
+    if (sw) hipLaunchKernelGGL((skinny_reduce_kernel<true, false, false>), g, b, 0, s, r);
+    else hipLaunchKernelGGL((skinny_reduce_kernel<false, false, false>), g, b, 0, s, r);
+    return launched("vl2_moe_gemm_skinny");
+}
+extern "C" int32_t vl2_moe_gemv_batched(const void* W, int64_t w_stride, int32_t ldw, const void* x, int32_t ldx, const int32_t* ids, const float* wts,
+                                        const void* res, int32_t ldres, void* y, int32_t ldy, int32_t S, int32_t E, int32_t k, int32_t N, int32_t K,
+                                        float eps, int32_t flags, void* stream) {
+    if (!W || !x || !ids || !y || S <= 0 || E <= 0 || k <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemv_batched: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemv_batched: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (S > 65535) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: S=%d tokens exceed the grid", S);
+    if (K % 8 || ldw % 8 || ldw < K || w_stride < (int64_t)N * ldw || ldx % 8 || ldx < K || !ALIGNED16(W) || !ALIGNED16(x) || !ALIGNED16(y))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: need K%%8==0, 16-byte aligned rows, ldw / ldx >= K, w_stride >= N*ldw");
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemv_batched: flags other than VL2_GEMM_SWIGLU not built");
+    hipStream_t s = ST(stream);
+    if (flags & VL2_GEMM_SWIGLU) {       // x [S, ldx] -> y [S * k, ldy]
+        if (N % 64 || K > 32704 || wts || res || ldy < N / 2) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: SWIGLU needs N%%64==0, K<=32704, ldy >= N/2 and no wts / res");
+        GemvArgs a{(const bf16_t*)W, (const bf16_t*)x, nullptr, nullptr, y, N, K, ldw, eps, nullptr, 0, 0, 0, 1};
+        hipLaunchKernelGGL(moe_gemv_gu_rows_kernel, dim3((N / 2 + 3) / 4, k, S), dim3(256), (size_t)K * 2, s, a, (const int*)ids, (long long)w_stride, ldy, ldx);
+        return launched("vl2_moe_gemv_batched");
+    }
+    if (!wts) return fail(VL2_E_BADARG, "vl2_moe_gemv_batched: the down form needs the routing weights");
+    if (ldx != K) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: the down form reads the SwiGLU rows [S * k, K] without a gap (ldx=%d K=%d)", ldx, K);
+    if (ldy < N || (res && ldres < N)) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: need ldy / ldres >= N (N=%d)", N);
+    const size_t lds = (size_t)k * K * 2;
+    if (lds > 160 * 1024) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: k * K * 2 bytes of activations must fit the LDS (k=%d K=%d)", k, K);
+    const dim3 g((N + 3) / 4, S), b(256);
+#define VL2_MOE_DOWN(KS) do { lds_attr<moe_gemv_down_rows_kernel<KS>>(160 * 1024); \
+        hipLaunchKernelGGL((moe_gemv_down_rows_kernel<KS>), g, b, lds, s, (const bf16_t*)W, (long long)w_stride, ldw, (const bf16_t*)x, (const int*)ids, wts, \
+                           (const bf16_t*)res, ldres, (bf16_t*)y, ldy, N, K); } while (0)
+    if (k == 1) VL2_MOE_DOWN(1); else if (k == 2) VL2_MOE_DOWN(2); else if (k == 3) VL2_MOE_DOWN(3); else VL2_MOE_DOWN(4);
+#undef VL2_MOE_DOWN
+    return launched("vl2_moe_gemv_batched");
 }
 
 #include "vl2_stage.inc"

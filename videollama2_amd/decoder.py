@@ -1128,7 +1128,8 @@ class HipMixtralDecoder(HipMistralDecoder):
     attention, RoPE, norms and lm_head of the parent, and in every layer a sparse MoE block (MixtralSparseMoeBlock) in place of the MLP --
     router, token grouping, grouped expert GEMMs and combine on csrc/k_moe.h.  Runs operator by operator (the stage calls are
     dense-only); every routing table stays on the device, so the prefill and the decode step both capture into graphs.
-    Single GPU, batch 1, 16-bit weights: tensor parallelism, fp8 weights and batched / continuous decoding raise NotImplementedError."""
+    Single GPU, 16-bit weights: tensor parallelism and fp8 weights raise NotImplementedError, and so does batched / continuous decoding
+    until `enable_moe_batch()` switches it on."""
 
     def __init__(self, cfg, state_dict, device="cuda", max_seq_len=4096, n_layers=None, tp_group=None, tp_shard=None, tp_local=None):
         if tp_group is not None or tp_shard is not None or tp_local is not None:
@@ -1160,19 +1161,88 @@ class HipMixtralDecoder(HipMistralDecoder):
         raise NotImplementedError("MoE (mixtral) decoder: the paged KV cache is not built for it (its batched decoding is not): keep the "
                                   "contiguous cache")
 
+    # The regimes of the batched step's MoE block, set from scripts/moe_batch_bench.py (profiles/r20_moe_batch_bench.jsonl):
+    MOE_GEMM_BATCH = 5      # below this many sequences: the solo step's GEMVs per token (a row is bit for bit the solo step, as below GEMM_BATCH
+    #                         on the dense decoders); from it on the grouped kernels
+    MOE_SKINNY_ROWS = 0     # up to this many sequences the grouped kernels are the grouped skinny-M GEMM (ops.moe_gemm_skinny), beyond it the
+    #                         prefill's tiled grouped GEMM (ops.moe_gemm).  0: the tiled form at every size -- it measured faster than the
+    #                         skinny form at every size from 5 to 64 (2 % at 5, 10 % at 16, 24 % at 64), so the skinny form serves no size by
+    #                         default; 64 selects it for 5 .. 64 sequences (tests, the benchmark's comparison)
+
+    @property
+    def moe_batch(self):
+        """Whether batched / continuous decoding is on (enable_moe_batch)."""
+        return getattr(self, "_moe_batch", False)
+
+    @torch.no_grad()
+    def enable_moe_batch(self, on=True):
+        """OPT-IN, off by default (with it off every refusal below stands word for word): batched prefill, `generate_batch`, hipGraph batch
+        steps and `serving.ContinuousBatcher` on this decoder, with per-request sampling as for the dense decoders.
+        The batched step's MoE block: below MOE_GEMM_BATCH sequences the solo step's GEMVs per token in one launch per form (a row is bit for
+        bit the solo step); from it on a grouped GEMM, in which every active expert's weights stream once per step for all the rows routed
+        to it (equal to the solo step to 16-bit rounding): the prefill's tiled grouped GEMM, or up to MOE_SKINNY_ROWS sequences the grouped
+        skinny-M GEMM (0 by default: it measured slower).  Still refused: a shared prefix,
+        the paged and the fp8 KV cache, fp8 / MXFP4 weights, tensor parallelism.  Switching drops the captured batch graphs and the slot
+        buffers; it is refused while a batcher holds requests in flight."""
+        busy = getattr(self, "_bb_busy", None)
+        if busy is not None and busy.in_flight():
+            raise RuntimeError("enable_moe_batch: a ContinuousBatcher holds requests in flight on this decoder's slots: drain it (run()) first")
+        self._moe_batch = bool(on)
+        self._invalidate_graphs()
+        self._bb = None
+        return self
+
     def prefill_batch(self, xs, caches, logits_out):
-        raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")
+        if not getattr(self, "_moe_batch", False):
+            raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")
+        # the scan kernel stages rows * k expert ids (csrc/k_moe.h MOE_SCAN_MAX): groups of at most that many rows, each bit for bit the
+        # prompts one by one (every kernel of the rows loop is row-independent)
+        cap, lens, b0 = self.MOE_SCAN_IDS // self.k, [], 0
+        while b0 < len(xs):
+            b1, rows = b0 + 1, xs[b0].shape[0]
+            while b1 < len(xs) and rows + xs[b1].shape[0] <= cap:
+                rows += xs[b1].shape[0]
+                b1 += 1
+            lens += super().prefill_batch(xs[b0:b1], caches[b0:b1], logits_out[b0:b1])
+            b0 = b1
+        return lens
+
+    MOE_SCAN_IDS = 16384     # csrc/k_moe.h MOE_SCAN_MAX
 
     def generate_batch(self, *args, **kwargs):
         if kwargs.get("shared_prefix") is not None:
             self._shared_prefix_refusals()
-        raise NotImplementedError("MoE (mixtral) decoder: batched decoding not built")
+        if not getattr(self, "_moe_batch", False):
+            raise NotImplementedError("MoE (mixtral) decoder: batched decoding not built")
+        return super().generate_batch(*args, **kwargs)
 
     def _shared_prefix_refusals(self, paged_ok=False):
         raise NotImplementedError("MoE (mixtral) decoder: shared-prefix decode is not built (its batched decoding is not)")
 
+    def moe_part_bytes(self, nb):
+        """Bytes of fp32 partial sums of the grouped skinny-M GEMMs of a step of nb <= 64 sequences: the larger of gate/up (N = 2I, K = D)
+        and down (N = D, K = I), each ks * nb*k * N * 4 with the skinny-M K split ks of its (N, K)."""
+        return max(ops.moe_skinny_part_bytes(nb, self.k, 2 * self.I, self.D), ops.moe_skinny_part_bytes(nb, self.k, self.D, self.I))
+
+    def _moe_step_buffers(self, B):
+        """The MoE block's buffers of a batched step for B slots: ids / weights [B, k], the compact tables, the normalised rows, the SwiGLU
+        rows [B*k, I], the down rows [B*k, D] and the fp32 partials of the grouped skinny-M GEMMs (for min(B, 64) rows)."""
+        bf = dict(dtype=_lib.elem_dtype(), device=self._dev)
+        i32 = dict(dtype=torch.int32, device=self._dev)
+        k = self.k
+        return dict(ids=torch.zeros((B, k), **i32), wts=torch.zeros((B, k), dtype=torch.float32, device=self._dev),
+                    counts=torch.zeros((self.E,), **i32), offs=torch.zeros((self.E + 1,), **i32), gather=torch.zeros((B * k,), **i32),
+                    inv=torch.zeros((B, k), **i32), h=torch.empty((B, self.D), **bf), a=torch.empty((B * k, self.I), **bf),
+                    y=torch.empty((B * k, self.D), **bf),
+                    part=torch.empty((self.moe_part_bytes(min(B, 64)) // 4,), dtype=torch.float32, device=self._dev))
+
     def _ensure_batch(self, B, owner=None):
-        raise NotImplementedError("MoE (mixtral) decoder: batched / continuous decoding not built")
+        if not getattr(self, "_moe_batch", False):
+            raise NotImplementedError("MoE (mixtral) decoder: batched / continuous decoding not built")
+        bb = super()._ensure_batch(B, owner)
+        if "moe" not in bb:
+            bb["moe"] = self._moe_step_buffers(bb["B"])
+        return bb
 
     def moe_block(self, lw, x1, rn):
         """x1 [S, D] (attention output + residual) -> x1 + MoE(RMSNorm(x1)); rn [S, 2] gets (0, rstd) of the result for the next
@@ -1187,9 +1257,9 @@ class HipMixtralDecoder(HipMistralDecoder):
 
     @torch.no_grad()
     def prefill(self, x, return_all_logits=False, cache=None, logits_out=None):
-        if cache is not None:
+        if cache is not None and not getattr(self, "_moe_batch", False):
             raise NotImplementedError("MoE (mixtral) decoder: external caches (batched decoding) not built")
-        return super().prefill(x, return_all_logits=return_all_logits, logits_out=logits_out)
+        return super().prefill(x, return_all_logits=return_all_logits, cache=cache, logits_out=logits_out)
 
     def _rows_block(self, f, li, o, x):
         """x1 = x + o_proj(o) on the tiled GEMM whatever the form (its norm is taken by the router), then the sparse MoE block (any row
@@ -1201,10 +1271,39 @@ class HipMixtralDecoder(HipMistralDecoder):
         """x1 = x + o_proj(o); router GEMV (+RMSNorm, softmax, top-k -> ids / weights on the device); gate/up+SwiGLU GEMV of the k chosen
         experts (one launch); down GEMV of both (one launch, weighted, + residual) into x.  No host read: the step replays as a graph."""
         lw = self.w["layers"][li]
+        if x.dim() == 2:
+            return self._token_block_batched(f, lw, o, x, x1)
         ops.gemv(lw["wo"], o, res=x, out=x1)
         ops.moe_route_gemv(x1, lw["wr"], self.moe_ids, self.moe_wts, self.eps)
         ops.moe_gemv(lw["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
         ops.moe_gemv(lw["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
+
+
+    def _token_block_batched(self, f, lw, o, x, x1):
+        """The same for the nb rows of a batched step (enable_moe_batch), on the slot buffers' MoE tensors: x1 = x + o_proj(o) through the
+        form, then one of three regimes by nb (class attributes MOE_GEMM_BATCH / MOE_SKINNY_ROWS).  No host read and, in the first two, no
+        allocation: the step captures into one hipGraph per batch size."""
+        nb, k, m = x.shape[0], self.k, self._bb["moe"]
+        R = nb * k
+        f.res(o, lw["wo"], x, out=x1)
+        ids, wts = m["ids"][:nb], m["wts"][:nb]
+        if nb < self.MOE_GEMM_BATCH:             # the solo step's GEMVs, a token index in the grid: every (token, slot) pair streams its expert
+            ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
+            ops.moe_gemv_batched(lw["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])
+            ops.moe_gemv_batched(lw["wd"], m["a"][:R], ids, wts=wts, res=x1, out=x)
+        elif nb <= self.MOE_SKINNY_ROWS:         # grouped skinny-M: an expert's weights stream once for all the rows routed to it
+            t = dict(counts=m["counts"], offs=m["offs"], gather=m["gather"][:R], inv=m["inv"][:nb], wts=wts)
+            ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts, tables=t)
+            h = ops.rmsnorm(x1, self.w["ones"], self.eps, out=m["h"][:nb])          # (the norm weight is folded into wgu)
+            ops.moe_gemm_skinny(h, lw["wgu"], t, nb, k, m["part"], rowmap=t["gather"], swiglu=True, out=m["a"][:R])
+            ops.moe_gemm_skinny(m["a"][:R], lw["wd"], t, nb, k, m["part"], out=m["y"][:R])
+            ops.moe_combine(x1, m["y"][:R], t, self.eps, out=x)
+        else:                                    # the prefill's sparse block on the nb rows (its tables are sized per call)
+            r = ops.moe_route(x1, lw["wr"], k, self.eps)
+            a = ops.moe_gemm(r["xg"], lw["wgu"], r, nb, k, swiglu=True, row_norm=r["rn"], eps=self.eps)
+            ops.moe_combine(x1, ops.moe_gemm(a, lw["wd"], r, nb, k), r, self.eps, out=x)
+            ids, wts = r["ids"], r["wts"]
+        self.last_route = dict(ids=ids, wts=wts)             # (of the last layer routed: tests follow the kernel's choice)
 
 
 def make_decoder(cfg, *args, **kwargs):

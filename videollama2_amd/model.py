@@ -435,6 +435,15 @@ class VideoLLaMA2Hip(nn.Module):
         self.decoder.enable_paged_kv(n_pages, on, fp8=fp8)
         return self
 
+    def enable_moe_batch(self, on=True):
+        """OPT-IN, Mixtral only: batched and continuous decoding on the sparse-MoE decoder (`HipMixtralDecoder.enable_moe_batch`, DESIGN.md
+        section 22): `generate_batch`, the padded-batch `generate` and `batcher()` then work as for the dense decoders.  Off by default; a
+        shared prefix, the paged and the fp8 KV cache and quantised weights stay refused for Mixtral."""
+        if not hasattr(self.decoder, "enable_moe_batch"):
+            raise NotImplementedError("enable_moe_batch: the decoder is dense (it has no MoE block, and batches without a switch)")
+        self.decoder.enable_moe_batch(on)
+        return self
+
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None):
         """Continuous batching over this model (serving.ModelBatcher): submit (input_ids, images) requests at any time, `step()`
         decodes one token for everything in flight, admission / retirement happen between steps."""

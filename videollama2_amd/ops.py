@@ -1173,3 +1173,60 @@ def moe_gemv(w, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
     _lib.call("vl2_moe_gemv", _p(w), w.stride(0), w.stride(1), _p(x), _p(ids), _p(wts), _p(res), _p(out), E, k, N, K, float(eps),
               GEMM_SWIGLU if swiglu else 0, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ batched MoE decode, csrc/k_moe_skinny.h
+def moe_route_rows(x, wr, k, eps, ids, wts, tables=None, logits=None):
+    """include/vl2hip.h vl2_moe_route_rows: route the rows x [S, D] into ids / wts [S, k] (device buffers, written in place) and, with
+    tables = dict(counts [E], offs [E+1], gather [S*k], inv [S, k]), the compact tables of the grouped skinny GEMM (row tile 1: no padding)."""
+    _chk(x, _lib.elem_dtype(), "x"); _chk(wr, torch.float32, "wr"); _chk(wts, torch.float32, "wts"); _chk(logits, torch.float32, "logits")
+    S, D = x.shape
+    E = wr.shape[0]
+    t = tables or {}
+    for name, n in (("ids", S * k), ("wts", S * k)) + ((("counts", E), ("offs", E + 1), ("gather", S * k), ("inv", S * k)) if tables else ()):
+        buf = {**t, "ids": ids, "wts": wts}[name]
+        if buf.numel() < n or not buf.is_contiguous():
+            raise ValueError(f"moe_route_rows: {name} needs {n} contiguous elements, got {tuple(buf.shape)}")
+    _lib.call("vl2_moe_route_rows", _p(x), x.stride(0), _p(wr), S, D, E, k, float(eps), _p(ids), _p(wts), _p(logits), _p(t.get("counts")),
+              _p(t.get("offs")), _p(t.get("gather")), _p(t.get("inv")), _stream())
+
+
+def moe_skinny_part_bytes(S, k, N, K):
+    """Bytes of fp32 partial sums moe_gemm_skinny needs for S tokens: ks * S*k * N * 4, ks = the skinny-M K split of (N, K)."""
+    n = int(_lib.load().vl2_moe_gemm_skinny_part_bytes(S, k, N, K))
+    if n < 0:
+        raise ValueError(f"moe_gemm_skinny: shape not built (S={S} k={k} N={N} K={K}: S <= 64, N % 64 == 0, K % 32 == 0)")
+    return n
+
+
+def moe_gemm_skinny(a, w, tables, S, k, part, rowmap=None, swiglu=False, out=None):
+    """include/vl2hip.h vl2_moe_gemm_skinny: the grouped skinny-M GEMM of S <= 64 tokens over the S*k permuted rows of the compact tables
+    (moe_route_rows).  a: the permuted rows [S*k, K], or with rowmap [S*k] (permuted row -> row of a) the token rows [S, K]; w [E, N, K]
+    (swiglu: each expert packed like pack_gate_up) -> [S*k, N] (swiglu [S*k, N/2]).  part: fp32 buffer of moe_skinny_part_bytes(S, k, N, K)."""
+    _chk(a, _lib.elem_dtype(), "a"); _chk(w, _lib.elem_dtype(), "w"); _chk(part, torch.float32, "part")
+    E, N, K = w.shape
+    R = S * k
+    if out is None:
+        out = torch.empty((R, N // 2 if swiglu else N), dtype=_lib.elem_dtype(), device=a.device)
+    if out.shape[0] < R or (rowmap is not None and rowmap.numel() < R) or tables["counts"].numel() < E or tables["offs"].numel() < E + 1:
+        raise ValueError("moe_gemm_skinny: out / rowmap / tables are too short for S * k rows and E experts")
+    _lib.call("vl2_moe_gemm_skinny", _p(a), a.stride(0), a.shape[0], _p(rowmap), _p(w), w.stride(0), w.stride(1), _p(out), out.stride(0),
+              _p(tables["counts"]), _p(tables["offs"]), S, k, E, N, K, GEMM_SWIGLU if swiglu else 0, _p(part), part.numel() * 4, _stream())
+    return out
+
+
+def moe_gemv_batched(w, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
+    """include/vl2hip.h vl2_moe_gemv_batched: moe_gemv for the S tokens of ids [S, k] in one launch.  swiglu=True: x [S, D] -> [S*k, N/2];
+    else x = the SwiGLU rows [S*k, K] -> [S, N] = res + sum_j wts[t, j] * W_{ids[t, j]} x[t*k + j].  A token's rows are moe_gemv's bits."""
+    _chk(w, _lib.elem_dtype(), "w"); _chk(x, _lib.elem_dtype(), "x"); _chk(res, _lib.elem_dtype(), "res"); _chk(wts, torch.float32, "wts")
+    E, N, K = w.shape
+    S, k = ids.shape
+    if x.shape[0] < (S if swiglu else S * k) or (res is not None and res.shape[0] < S) or (wts is not None and wts.numel() < S * k):
+        raise ValueError("moe_gemv_batched: x / res / wts are too short for the S tokens of ids")
+    if out is None:
+        out = torch.empty((S * k, N // 2) if swiglu else (S, N), dtype=_lib.elem_dtype(), device=w.device)
+    if out.shape[0] < (S * k if swiglu else S):
+        raise ValueError("moe_gemv_batched: out is too short for the S tokens of ids")
+    _lib.call("vl2_moe_gemv_batched", _p(w), w.stride(0), w.stride(1), _p(x), x.stride(0), _p(ids), _p(wts), _p(res),
+              0 if res is None else res.stride(0), _p(out), out.stride(0), S, E, k, N, K, float(eps), GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
