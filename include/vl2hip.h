@@ -436,6 +436,17 @@ int32_t vl2_attn_decode_kv8_paged(const void* qkv, void* k8pool, void* v8pool, f
                                   float scale, void* stream);
 int32_t vl2_kv_page_quant(const void* k16, const void* v16, void* k8pool, void* v8pool, float* kspool, float* vspool, const int32_t* table_row,
                           int32_t nkv, int32_t smax, int32_t n_pages, int32_t p0, int32_t p1, void* stream);
+/* ---- swapping pages of the paged KV cache (csrc/k_kv_swap.h; an addition of ABI 7; OPTIONAL): the only data path of a preemption
+ * (DESIGN.md section 23).  A page is opaque: page_bytes bytes, a positive multiple of 16 -- [nkv, 64, 128] 16-bit elements, [nkv, 64, 128] e4m3fn
+ * codes or [nkv, 64] fp32 row scales, so one call form serves every pool kind above.
+ * vl2_kv_pages_move: n whole pages of ONE pool tensor pool = [n_pages][page_bytes] to or from the packed DEVICE arena = [n][page_bytes].
+ *   page_ids: device int32 [n].  to_arena != 0: pool page page_ids[i] -> arena slot i (gather); to_arena == 0: arena slot i -> pool page
+ *   page_ids[i] (scatter), byte for byte.  An id outside [1, n_pages) is skipped (page 0 is the parking page and is never moved) and its arena
+ *   slot or pool page is left untouched; nothing but the n arena slots (gather) or the named pages (scatter) is written.  n == 0: nothing, no
+ *   launch; 0 <= n <= 65535.  Both pointers are device memory at 16-byte alignment: the host leg of a swap is a copy between the arena and
+ *   pinned host memory on the same stream. */
+int32_t vl2_kv_pages_move(void* pool, void* arena, const int32_t* page_ids, int32_t n, int32_t n_pages, int64_t page_bytes, int32_t to_arena,
+                          void* stream);
 /* greedy argmax (first maximal index) of fp32 logits -> *tok (device int32) and hist[step] if hist != NULL.
  * state != NULL (device int32[2] = {position, step}): hist index = state[1], then both counters advance by one, so the
  * whole decode step is replayable from a hipGraph.  HF:generation/utils.py _sample with do_sample=False. */

@@ -44,6 +44,7 @@ static constexpr bool kLab = false;
 #include "k_attn_paged.h"
 #include "k_attn_paged_shared.h"
 #include "k_attn_paged_kv8.h"
+#include "k_kv_swap.h"
 
 static thread_local char g_err[512] = "";
 static int32_t fail(int32_t code, const char* fmt, ...) {
@@ -1397,6 +1398,26 @@ extern "C" int32_t vl2_kv_page_quant(const void* k16, const void* v16, void* k8p
     hipLaunchKernelGGL(kv_page_quant_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, ST(stream), (const bf16_t*)k16, (const bf16_t*)v16,
                        (uint8_t*)k8pool, (uint8_t*)v8pool, kspool, vspool, (const int*)table_row, nkv, smax, n_pages, p0, p1);
     return launched("vl2_kv_page_quant");
+}
+// ---- swapping pages of the paged KV cache (k_kv_swap.h): n whole pages of ONE pool tensor to or from a packed device arena
+extern "C" int32_t vl2_kv_pages_move(void* pool, void* arena, const int32_t* page_ids, int32_t n, int32_t n_pages, int64_t page_bytes,
+                                     int32_t to_arena, void* stream) {
+    if (!pool || !arena || !page_ids) return fail(VL2_E_BADARG, "vl2_kv_pages_move: null pointer");
+    if (n < 0 || n > 65535) return fail(VL2_E_BADARG, "vl2_kv_pages_move: n %d outside [0, 65535]", n);
+    if (n_pages < 1) return fail(VL2_E_SHAPE, "vl2_kv_pages_move: n_pages %d: the pool holds at least the parking page", n_pages);
+    if (page_bytes <= 0 || (page_bytes & 15))
+        return fail(VL2_E_SHAPE, "vl2_kv_pages_move: page_bytes %lld must be a positive multiple of 16", (long long)page_bytes);
+    if (!ALIGNED16(pool) || !ALIGNED16(arena)) return fail(VL2_E_SHAPE, "vl2_kv_pages_move: need a 16-byte aligned pool and arena");
+    if (n == 0) return 0;
+    // memory bound: about 2048 workgroups in all, each lane KV_MOVE_UNROLL 16-byte vectors per trip
+    const long vpp = (long)(page_bytes / 16);
+    const long per_wg = (long)KV_MOVE_UNROLL * 256;
+    long gx = (vpp + per_wg - 1) / per_wg;
+    const long cap = 2048 / n > 0 ? 2048 / n : 1;
+    if (gx > cap) gx = cap;
+    hipLaunchKernelGGL(kv_pages_move_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, ST(stream), (u32x4*)pool, (u32x4*)arena,
+                       (const int*)page_ids, n_pages, vpp, to_arena);
+    return launched("vl2_kv_pages_move");
 }
 extern "C" int32_t vl2_argmax(const float* logits, int32_t V, int32_t* tok, int32_t* hist, int32_t step, int32_t* state,
                               void* stream) {

@@ -334,7 +334,8 @@ class HipMistralDecoder(nn.Module):
         into its pages.  Switching drops every captured batch graph and the slot buffers; it is refused while a batcher holds requests in
         flight.  The single-sequence paths (`generate`, `extend`, the prefix cache) keep their contiguous cache and are untouched.
         Tensor parallelism, head_dim != 128, Mixtral, the fp8 KV cache (each switch refuses the other) and
-        `generate_batch(shared_prefix=...)` raise NotImplementedError.  Not built: growing a reservation page by page, preemption.
+        `generate_batch(shared_prefix=...)` raise NotImplementedError.  Growing a reservation page by page and preemption by swap:
+        `ContinuousBatcher(reserve="grow")`; `generate_batch` keeps reserving up front.
         fp8=True (csrc/k_attn_paged_kv8.h): the pages hold the rows of the fp8 KV cache -- e4m3fn codes and one
         power-of-two scale per (kv head, row), `enable_fp8_kv`'s format -- so a page is `kv_page_bytes()` = 0.52 x the 16-bit page and every
         batched result is bit for bit that of contiguous fp8-KV slots (a decoder with `enable_fp8_kv()`): the staging rows are quantised into

@@ -444,11 +444,11 @@ class VideoLLaMA2Hip(nn.Module):
         self.decoder.enable_moe_batch(on)
         return self
 
-    def batcher(self, max_slots=4, eos_token_id=None, use_graph=None):
+    def batcher(self, max_slots=4, eos_token_id=None, use_graph=None, reserve="whole"):
         """Continuous batching over this model (serving.ModelBatcher): submit (input_ids, images) requests at any time, `step()`
         decodes one token for everything in flight, admission / retirement happen between steps."""
         from .serving import ModelBatcher
-        return ModelBatcher(self, max_slots, eos_token_id, use_graph)
+        return ModelBatcher(self, max_slots, eos_token_id, use_graph, reserve)
 
     @torch.no_grad()
     def generate_batch(self, requests, **kwargs):

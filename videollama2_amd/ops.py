@@ -720,6 +720,38 @@ def kv_page_quant(kcache, vcache, pools8, table_row, p0, p1):
               p0, p1, _stream())
 
 
+def kv_pages_move(pool, arena, page_ids, to_arena):
+    """include/vl2hip.h vl2_kv_pages_move: the n = len(page_ids) whole pages of ONE pool tensor that page_ids (int32 [n], contiguous) names to
+    (to_arena=True) or from (False) slots 0 .. n-1 of the packed device arena, byte for byte.  pool: contiguous, one of the three pool kinds --
+    [n_pages, nkv, 64, 128] of the build's 16-bit type or of uint8 codes, [n_pages, nkv, 64] of fp32 row scales; arena: contiguous, the pool's
+    dtype and page shape, at least n slots.  An id outside [1, n_pages) is skipped.  Everything is checked here, before the library is called;
+    n == 0 returns after the checks without calling it (an empty tensor has no address to hand over)."""
+    kinds = ((_lib.elem_dtype(), (KV_PAGE_ROWS, 128)), (torch.uint8, (KV_PAGE_ROWS, 128)), (torch.float32, (KV_PAGE_ROWS,)))
+    if pool.dtype not in [k[0] for k in kinds]:
+        raise TypeError(f"kv_pages_move: pool must be {_lib.elem_dtype()} rows, torch.uint8 codes or torch.float32 row scales, got {pool.dtype}")
+    _dtypes("kv_pages_move", (arena, pool.dtype, "arena"), (page_ids, torch.int32, "page_ids"))
+    tail = dict(kinds)[pool.dtype]
+    if pool.dim() != 2 + len(tail) or tuple(pool.shape[2:]) != tail or pool.shape[0] < 1 or pool.shape[1] < 1:
+        raise ValueError(f"kv_pages_move: a {pool.dtype} pool must be [n_pages, nkv, {', '.join(map(str, tail))}], got {tuple(pool.shape)}")
+    if not (pool.is_contiguous() and arena.is_contiguous()):
+        raise ValueError("kv_pages_move: the pool's and the arena's pages must be contiguous")
+    if page_ids.dim() != 1 or not page_ids.is_contiguous():
+        raise ValueError(f"kv_pages_move: page_ids must be a contiguous int32 vector, got {tuple(page_ids.shape)}")
+    n = page_ids.numel()
+    if arena.dim() != pool.dim() or arena.shape[1:] != pool.shape[1:] or arena.shape[0] < n:
+        raise ValueError(f"kv_pages_move: the arena must hold at least {n} pages of {tuple(pool.shape[1:])}, got {tuple(arena.shape)}")
+    page_bytes = pool.stride(0) * pool.element_size()
+    if page_bytes % 16:
+        raise ValueError(f"kv_pages_move: a page of {page_bytes} bytes is no multiple of 16")
+    for t, name in ((pool, "pool"), (arena, "arena"), (page_ids, "page_ids")):
+        _chk(t, t.dtype, name)
+    if not (pool.device == arena.device == page_ids.device):
+        raise ValueError(f"kv_pages_move: pool, arena and page_ids must be on one device, got {pool.device}, {arena.device}, {page_ids.device}")
+    if n == 0:
+        return
+    _lib.call("vl2_kv_pages_move", _p(pool), _p(arena), _p(page_ids), n, pool.shape[0], page_bytes, 1 if to_arena else 0, _stream())
+
+
 def attn_decode_kv8_paged(qkv, pools8, table, cos_t, sin_t, partial, out, nh, nkv, pos_dev, ctx_cap, scale):
     """include/vl2hip.h vl2_attn_decode_kv8_paged: `attn_decode_kv8_batched` on the paged fp8 cache.  qkv [B, (nh+2nkv)*128] un-roped, pools8 =
     (k8pool, v8pool, kspool, vspool): codes uint8 [n_pages, nkv, 64, 128] and scales fp32 [n_pages, nkv, 64]; table, out, pos_dev, seq_cap,

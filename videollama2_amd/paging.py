@@ -7,7 +7,11 @@ it is never handed out, and the table row of a slot that holds no request points
 at position 0 reads and writes finite, harmless rows.
 
 A resident prefix (kernels: csrc/k_attn_paged_shared.h) shares the WHOLE pages of a prompt prefix among the requests of a
-batcher: `shared_rows`, a request's own reservation `own_pages_needed` and the row of an empty slot behind the prefix, `prefix_parked_row`."""
+batcher: `shared_rows`, a request's own reservation `own_pages_needed` and the row of an empty slot behind the prefix, `prefix_parked_row`.
+
+Reservations that grow page by page (`ContinuousBatcher(reserve="grow")`): `rows_next`, the rows a request needs a
+page for before its next step; `plan_growth`, one step's grants and the requests preempted to serve them; `admit_grow`, admission on the
+pages of the prompt with headroom."""
 
 PAGE_ROWS = 64
 PARKING_PAGE = 0
@@ -89,6 +93,68 @@ class PagePool:
         if len(set(ids)) != len(ids):
             raise ValueError(f"PagePool.free: a page is named twice in {ids} (double free)")
         self._free.update(ids)
+
+
+def rows_next(S, n_tokens, max_seq_len):
+    """Rows that must have a page before the next step of a request of S prompt rows that has emitted n_tokens: min(S + n_tokens + 1,
+    max_seq_len).  Step k emits token k and writes row S + k, so ceil(rows_next(S, max_new - 1, ...) / 64) == pages_needed(S, max_new, ...):
+    a request that grows page by page ends on its whole reservation and never exceeds it."""
+    return min(int(S) + int(n_tokens) + 1, int(max_seq_len))
+
+
+def pages_for(rows):
+    """Pages that hold `rows` rows: ceil(rows / 64)."""
+    return (int(rows) + PAGE_ROWS - 1) // PAGE_ROWS
+
+
+def plan_growth(in_flight, free_pages):
+    """The growth and preemption decision of one step under reserve="grow" (DESIGN.md section 23).  in_flight: (admission order, pages held,
+    rows_next) per request in flight, any order; free_pages: what the pool holds.  Every request must hold ceil(rows_next / 64) pages before
+    the step.  Grants go oldest first; when the pool cannot serve a grant the NEWEST admitted request still in flight is taken as a victim
+    (possibly the requester itself): its pages count as free and its own grant is dropped.  No victim is taken while the free pages suffice,
+    and the oldest request is never one: a pool that cannot serve it alone raises RuntimeError (`submit` refuses such a request).
+    Returns (grants, victims): grants = [(admission order, pages to add > 0)] oldest first, victims = [admission order] newest first."""
+    alive = sorted((int(o), int(held), max(0, pages_for(rows) - int(held))) for o, held, rows in in_flight)
+    free = int(free_pages)
+    grants, victims = [], []
+    i = 0
+    while i < len(alive):
+        order, held, want = alive[i]
+        if want <= free:
+            free -= want
+            if want:
+                grants.append((order, want))
+            i += 1
+            continue
+        if len(alive) == 1:
+            raise RuntimeError(f"plan_growth: the oldest request holds {held} pages and needs {want} more, the pool has {free} free with "
+                               f"nobody left to preempt")
+        v_order, v_held, _ = alive.pop()        # the newest admitted; i itself when it is the last one alive (then the loop ends)
+        victims.append(v_order)
+        free += v_held
+    return grants, victims
+
+
+def admit_grow(queue_needs, free_slots, free_pages, n_in_flight):
+    """Admission of one step under reserve="grow".  queue_needs: the pages each queued request must get NOW, in queue order (a new request:
+    ceil(rows_next / 64) of its prompt; a resumed one: the same of its position, i.e. its saved pages, plus one at a page edge).  Strict FIFO:
+    the head joins only if a slot is free, the pool holds its pages, and afterwards one free page per request then in flight (itself
+    included) remains as headroom -- so that admission does not cause the next step's preemption.  The headroom rule is waived for a step
+    that begins with nothing in flight (n_in_flight == 0): an idle batcher fills its slots on the pages of the prompts alone, and a request
+    that fills the pool alone can start.  Returns how many requests from the head are admitted."""
+    n = 0
+    free_slots, free_pages, n_in_flight = int(free_slots), int(free_pages), int(n_in_flight)
+    headroom = n_in_flight > 0
+    for need in queue_needs:
+        if free_slots <= 0 or need > free_pages:
+            break
+        if headroom and free_pages - need < n_in_flight + 1:
+            break
+        free_slots -= 1
+        free_pages -= need
+        n_in_flight += 1
+        n += 1
+    return n
 
 
 def admit_fifo(needs, free_slots, free_pages):

@@ -19,17 +19,19 @@ import torch
 
 from . import _lib
 from .decoder import eos_set
-from .paging import PAGE_ROWS, admit_fifo, own_pages_needed, pages_needed, parked_row, prefix_parked_row, shared_rows, table_row
+from .paging import (PAGE_ROWS, admit_fifo, admit_grow, own_pages_needed, pages_for, pages_needed, parked_row, plan_growth, prefix_parked_row,
+                     rows_next, shared_rows, table_row)
 
 
 class _Request:
-    __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done", "sampler", "u", "need", "pages")
+    __slots__ = ("rid", "x", "max_new", "streamer", "criteria", "tokens", "slot", "done", "sampler", "u", "need", "pages", "S", "order", "swap")
 
     def __init__(self, rid, x, max_new, streamer, criteria, sampler=None, u=None):
         self.rid, self.x, self.max_new, self.streamer, self.criteria = rid, x, max_new, streamer, criteria
         self.sampler, self.u = sampler, u              # (temperature, top_k, top_p) and the request's uniform numbers, or None: greedy
         self.tokens, self.slot, self.done = [], None, False
         self.need, self.pages = 0, None                # paged KV: the reservation (pages) and, once admitted, the page ids
+        self.S, self.order, self.swap = 0, None, None  # reserve="grow": prompt rows, admission order, and while swapped out (pinned pages, logits row)
 
 
 class PrefixHandle:
@@ -57,7 +59,16 @@ class ContinuousBatcher:
     the WHOLE reservation (`paging.admit_fifo`): the head of the queue joins only when a slot is free and the pool holds all its pages,
     otherwise nobody is admitted in that step -- so no request can run out of pages in flight and the step's graph replays untouched (it reads
     the page table from the device).  A request's tokens are bit for bit the contiguous slots'.  A request that can never fit the pool is
-    refused at `submit`.  Not built: growing a reservation page by page, preemption.  The decoder refuses the switch with requests in flight.
+    refused at `submit`.  The decoder refuses the switch with requests in flight.
+    reserve="grow" (needs the paged KV cache, 16-bit or fp8 pages; the default "whole" is everything above, untouched): the
+    pool follows the rows that exist.  A request is admitted on the pages of its prompt (`paging.admit_grow`), takes one more page each time it
+    crosses a 64-row edge (one `_set_table_rows` copy; the captured step graphs read the table from the device and are never re-captured), and
+    when the pool is dry the newest admitted request is SWAPPED OUT (`paging.plan_growth`): its pages go through one small device arena
+    (`ops.kv_pages_move`) into pinned host memory, byte for byte, with its row of logits; its slot and pages are freed, and it waits in
+    `swapped`, which is served before `waiting`, oldest first.  A resumed request may land in another slot and on other page ids.  Nothing is
+    recomputed, so a request's tokens stay bit for bit those of its solo decode.  `submit` still refuses a request whose WORST-CASE reservation
+    exceeds the pool: that is what lets the oldest request always finish alone.  `preemptions` / `resumes` count the events.  Not built: growth
+    behind a resident prefix (`open_prefix` is refused), a cap on host swap memory, growth in `generate_batch`, recompute-style preemption.
     fp8 pages (decoder.enable_paged_kv(n_pages, fp8=True)): the same reservations, admission and retirement on pages of
     fp8 rows; a request is prefilled into the staging cache and quantised into its pages, and its tokens are bit for bit those of the
     contiguous fp8-KV slots.  A resident prefix is refused on them.
@@ -68,9 +79,22 @@ class ContinuousBatcher:
     `generate_batch([cat(x_prefix[Pf:], suffix)], shared_prefix=x_prefix[:Pf])` on an unpaged decoder, Pf = the shared rows.  One prefix at a
     time; `close_prefix()` returns its pages."""
 
-    def __init__(self, decoder, max_slots=4, eos_token_id=None, use_graph=None):
+    reserve = "whole"           # the reservation policy: "whole" (admission to retirement) | "grow" (page by page, preemption by swap)
+    swapped = ()                # (reserve="grow": the requests swapped out to host memory)
+
+    def __init__(self, decoder, max_slots=4, eos_token_id=None, use_graph=None, reserve="whole"):
         if decoder.tp > 1:
             raise NotImplementedError("continuous batching is built for the single-GPU decoder")
+        if reserve not in ("whole", "grow"):
+            raise ValueError(f"ContinuousBatcher: reserve must be \"whole\" or \"grow\", got {reserve!r}")
+        if reserve == "grow" and not decoder.paged_kv:
+            raise RuntimeError("ContinuousBatcher: reserve=\"grow\" grows reservations in the page pool: call decoder.enable_paged_kv(n_pages) "
+                               "first")
+        self.reserve = reserve
+        self.swapped = collections.deque()      # reserve="grow": the requests swapped out to host memory, oldest first
+        self.preemptions = self.resumes = 0
+        self._orders = itertools.count()
+        self._arena = {}                        # reserve="grow": one reusable device arena of pages_per_seq pages per pool kind
         self.dec = decoder
         self.max_slots = int(max_slots)
         self.eos = eos_set(eos_token_id)
@@ -128,6 +152,9 @@ class ContinuousBatcher:
     def _open_prefix_refusals(self):
         """The refusals of open_prefix that do not depend on the prefix (ModelBatcher.open_video makes them before the encoder runs)."""
         dec = self.dec
+        if self.reserve == "grow":
+            raise NotImplementedError("open_prefix: this batcher grows its reservations page by page (reserve=\"grow\") and growth behind a "
+                                      "resident prefix is not built: use a reserve=\"whole\" batcher")
         dec._shared_prefix_refusals(paged_ok=True)       # everything the shared-prefix mode refuses, except paging itself
         if not dec.paged_kv:
             raise RuntimeError("open_prefix: the resident prefix lives in the page pool: call decoder.enable_paged_kv(n_pages) first")
@@ -170,6 +197,9 @@ class ContinuousBatcher:
         these, and it reserves only the pages behind the prefix's whole pages.  While a prefix is open every request names it."""
         from .model import UNBUILT_WARPERS, resolve_sampler
         h = self._prefix
+        if prefix is not None and self.reserve == "grow":
+            raise NotImplementedError("submit: this batcher grows its reservations page by page (reserve=\"grow\") and growth behind a resident "
+                                      "prefix is not built: submit without prefix=, or use a reserve=\"whole\" batcher")
         if prefix is not h:
             if prefix is None:
                 raise ValueError("submit: a prefix is open on this batcher: pass prefix=handle (plain and prefix requests do not share a step), "
@@ -210,9 +240,112 @@ class ContinuousBatcher:
             u = torch.rand((max_new,), device=self.dec._dev, generator=sampler[3])
             sampler = sampler[:3]
         r = _Request(next(self._ids), inputs_embeds, max_new, streamer, crit, sampler, u)
-        r.need = need
+        r.need, r.S = need, S
         self.waiting.append(r)
         return r.rid
+
+    # ---- reserve="grow": growth, preemption by swap, admission on the pages of the prompt
+    def _pos(self, r):
+        """The position of r's next token = the rows its cache holds: host arithmetic, no device read."""
+        return r.S + len(r.tokens)
+
+    def _pools_of(self, li):
+        """Layer li's pool tensors, every kind: (kpool, vpool) on 16-bit pages, (k8pool, v8pool, kspool, vspool) on fp8 pages."""
+        bb = self.bb
+        return bb["pools8"][li] if "pools8" in bb else (bb["kpool"][li], bb["vpool"][li])
+
+    def _arena_for(self, pool):
+        """The reusable device arena of pages_per_seq pages for pools of this dtype and page shape."""
+        key = (pool.dtype, tuple(pool.shape[1:]))
+        a = self._arena.get(key)
+        if a is None or a.device != pool.device or a.shape[0] != self.bb["pages_per_seq"]:
+            a = self._arena[key] = torch.empty((self.bb["pages_per_seq"],) + key[1], dtype=pool.dtype, device=pool.device)
+        return a
+
+    def _grow(self):
+        """Growth and preemption before a step.  Returns whether a request was preempted."""
+        bb, dec = self.bb, self.dec
+        live = {r.order: r for r in self.slots if r is not None}
+        grants, victims = plan_growth([(o, len(r.pages), rows_next(r.S, len(r.tokens), dec.max_seq_len)) for o, r in live.items()],
+                                      bb["pool"].n_free)
+        for o in victims:
+            self._swap_out(live[o])
+        for o, n in grants:                     # the new page into the request's table row: one small H2D copy, the graphs replay untouched
+            r = live[o]
+            r.pages = r.pages + bb["pool"].alloc(n)
+            dec._set_table_rows(r.slot, [table_row(r.pages, bb["pages_per_seq"])])
+        return bool(victims)
+
+    def _swap_out(self, r):
+        """Preempt r: its pages, layer by layer and pool by pool, through the arena into pinned host tensors kept on the request; its logits
+        row; its table row parked, its pages and slot freed.  Everything is enqueued on the current stream: stream order is the only
+        synchronisation, and whoever gets the pages next writes them later on the same stream."""
+        from . import ops
+        bb, dec = self.bb, self.dec
+        n = len(r.pages)
+        ids = torch.tensor(r.pages, dtype=torch.int32).to(dec._dev)
+        pinned = dec._dev.type == "cuda"
+        saved = []
+        for li in range(dec.n_layers):
+            for pool in self._pools_of(li):
+                arena = self._arena_for(pool)
+                ops.kv_pages_move(pool, arena, ids, True)
+                host = torch.empty((n,) + tuple(pool.shape[1:]), dtype=pool.dtype, pin_memory=pinned)
+                host.copy_(arena[:n], non_blocking=True)
+                saved.append(host)
+        r.swap = (saved, bb["logits"][r.slot].clone())
+        bb["pool"].free(r.pages)
+        dec._set_table_rows(r.slot, [parked_row(bb["pages_per_seq"])])
+        self.slots[r.slot] = None
+        r.slot, r.pages = None, None
+        self.swapped.append(r)
+        self.swapped = collections.deque(sorted(self.swapped, key=lambda q: q.order))
+        self.preemptions += 1
+
+    def _swap_in(self, r, slot):
+        """Resume r in `slot` on the pages r.pages (already in the slot's table row): the saved pages back into the first of them, the logits
+        row restored; the pinned buffers are released."""
+        from . import ops
+        bb, dec = self.bb, self.dec
+        saved, logits = r.swap
+        n = saved[0].shape[0]
+        ids = torch.tensor(r.pages[:n], dtype=torch.int32).to(dec._dev)
+        it = iter(saved)
+        for li in range(dec.n_layers):
+            for pool in self._pools_of(li):
+                arena = self._arena_for(pool)
+                arena[:n].copy_(next(it), non_blocking=True)
+                ops.kv_pages_move(pool, arena, ids, False)
+        bb["logits"][slot].copy_(logits)
+        bb["pos"][slot:slot + 1].fill_(self._pos(r))
+        r.swap = None
+        self.resumes += 1
+
+    def _admit_grow(self):
+        """Admission under reserve="grow": the swapped requests first (oldest first), then the waiting ones, strict FIFO over both."""
+        bb, dec = self.bb, self.dec
+        queue = list(self.swapped) + list(self.waiting)
+        needs = [pages_for(rows_next(r.S, len(r.tokens), dec.max_seq_len)) for r in queue]
+        free = [s for s, r in enumerate(self.slots) if r is None]
+        take = admit_grow(needs, len(free), bb["pool"].n_free, self.max_slots - len(free))
+        for r, need, slot in zip(queue[:take], needs, free):
+            (self.swapped if r.swap is not None else self.waiting).popleft()
+            r.pages = bb["pool"].alloc(need)
+            dec._set_table_rows(slot, [table_row(r.pages, bb["pages_per_seq"])])
+            if r.swap is not None:
+                self._swap_in(r, slot)
+            else:
+                r.order = next(self._orders)
+                dec.prefill_slot(slot, r.x, bb["logits"][slot])
+                bb["pos"][slot:slot + 1].fill_(r.S)
+                r.x = None
+            T, k, p = r.sampler if r.sampler is not None else (0.0, 0, 1.0)
+            bb["samp_T"][slot:slot + 1].fill_(T); bb["samp_k"][slot:slot + 1].fill_(k); bb["samp_p"][slot:slot + 1].fill_(p)
+            bb["sstep"][slot:slot + 1].fill_(len(r.tokens))            # a sampled request has drawn one number per token
+            if r.u is not None:                  # kept on the request: a resumed one fills another slot's row with it
+                bb["u"][slot, :r.u.numel()].copy_(r.u)
+            r.slot = slot
+            self.slots[slot] = r
 
     def _admit(self):
         bb, dec = self.bb, self.dec
@@ -267,7 +400,13 @@ class ContinuousBatcher:
                 raise RuntimeError("the decoder's batch buffers were reallocated while requests were in flight: use one batcher per decoder "
                                    "and do not call generate_batch() with more sequences than max_slots on it")
             self.bb = self.dec._bb            # no slot is occupied, so no request's rows were lost: go on in the new buffers
-        self._admit()
+        if self.reserve == "grow":
+            if not self.dec.paged_kv:
+                raise RuntimeError("reserve=\"grow\": the decoder's paged KV cache was switched off under this batcher")
+            if not self._grow():              # (no admission in a step that preempted)
+                self._admit_grow()
+        else:
+            self._admit()
         occupied = [s for s, r in enumerate(self.slots) if r is not None]
         if not occupied:
             return {}
@@ -317,7 +456,7 @@ class ContinuousBatcher:
             self.dec._set_table_rows(slot, [parked_row(pps) if h is None else prefix_parked_row(h.pages, pps)])
 
     def in_flight(self):
-        return sum(r is not None for r in self.slots) + len(self.waiting)
+        return sum(r is not None for r in self.slots) + len(self.waiting) + len(self.swapped)
 
     def run(self):
         """Step until nothing is waiting or in flight.  Returns {request id: LongTensor [n_new]} of everything finished so far."""
@@ -330,9 +469,9 @@ class ModelBatcher:
     """The same loop one level up: requests are (input_ids, images) pairs exactly as `VideoLLaMA2Hip.generate(inputs, images=)`
     takes them; the video is encoded and spliced at submission, the decode steps are shared."""
 
-    def __init__(self, model, max_slots=4, eos_token_id=None, use_graph=None):
+    def __init__(self, model, max_slots=4, eos_token_id=None, use_graph=None, reserve="whole"):
         self.model = model
-        self.inner = ContinuousBatcher(model.decoder, max_slots, eos_token_id, use_graph)
+        self.inner = ContinuousBatcher(model.decoder, max_slots, eos_token_id, use_graph, reserve)
 
     @torch.no_grad()
     def open_video(self, input_ids_prefix, images):
