@@ -20,7 +20,9 @@ def emulated_backend():
     lib.vl2_stc_workspace_bytes.argtypes = [ctypes.POINTER(_lib.StcDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     lib.vl2_llm_workspace_bytes.restype = ctypes.c_int64
     lib.vl2_llm_workspace_bytes.argtypes = [ctypes.POINTER(_lib.LlmDesc), ctypes.c_int32]
-    for name, args in {**_lib.SIGNATURES, **_lib.FP8_BATCH_SIGNATURES}.items():
+    lib.vl2_moe_gemm_skinny_part_bytes.restype = ctypes.c_int64
+    lib.vl2_moe_gemm_skinny_part_bytes.argtypes = [ctypes.c_int32] * 4
+    for name, args in {**_lib.SIGNATURES, **_lib.FP8_BATCH_SIGNATURES, **_lib.MOE_SIGNATURES, **_lib.MOE_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = ctypes.c_int32
         fn.argtypes = args

@@ -22,6 +22,8 @@ alignas(64) unsigned char vl2_smem[160 * 1024];
 #include "skinny_plan.h"
 #include "k_pack.h"
 #include "k_sample.h"
+#include "k_moe.h"
+#include "k_moe_skinny.h"
 #include <cstdint>
 #include <algorithm>
 #include <vector>
@@ -731,5 +733,179 @@ static int32_t fail(int32_t code, const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
+}
+// ------------------------------------------------------------------------------------------------ sparse MoE (k_moe.h, k_moe_skinny.h)
+// The argument checks are vl2_abi.hip's, in its order and with its messages: every check precedes every launch.
+#define EMU_ALIGNED16(p) ((((uintptr_t)(p)) & 15) == 0)
+static bool moe_rows_ok(int S, int k, int E, int P) {
+    return P % MOE_BM == 0 && (int64_t)P >= (int64_t)S * k + (int64_t)E * (MOE_BM - 1);
+}
+extern "C" int32_t vl2_moe_route(const void* x, int32_t ldx, const float* wr, int32_t S, int32_t D, int32_t E, int32_t k, float eps,
+                                 int32_t* ids, float* wts, float* rstd, float* logits, int32_t* counts, int32_t* offs, int32_t* gather,
+                                 int32_t* inv, int32_t P, void* xg, float* rn_g, void*) {
+    if (!x || !wr || !ids || !wts || !rstd || !counts || !offs || !gather || !inv || S <= 0 || D <= 0 || E <= 0 || k <= 0)
+        return fail(VL2_E_BADARG, "vl2_moe_route: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_route: need E <= %d and 1 <= k <= min(E, %d) (E=%d k=%d)", MOE_MAX_E, MOE_MAX_K, E, k);
+    if ((int64_t)S * k > MOE_SCAN_MAX) return fail(VL2_E_UNSUPP, "vl2_moe_route: S * k <= %d (S=%d k=%d)", MOE_SCAN_MAX, S, k);
+    if (D % 8 || ldx % 8 || ldx < D || !EMU_ALIGNED16(x) || !EMU_ALIGNED16(wr) || (xg && !EMU_ALIGNED16(xg)))
+        return fail(VL2_E_SHAPE, "vl2_moe_route: need D%%8==0, ldx>=D and 16-byte aligned rows (D=%d ldx=%d)", D, ldx);
+    if (!moe_rows_ok(S, k, E, P)) return fail(VL2_E_SHAPE, "vl2_moe_route: P=%d must be a multiple of %d and >= S*k + E*%d", P, MOE_BM, MOE_BM - 1);
+    if (xg && !rn_g) return fail(VL2_E_BADARG, "vl2_moe_route: the gathered rows need their row-norm table rn_g");
+    emu::launch(dim3((S + 3) / 4), dim3(256), [=] { moe_router_kernel((const bf16_t*)x, ldx, wr, S, D, E, k, eps, ids, wts, rstd, logits); });
+    emu::launch(dim3(1), dim3(1024), [=] { moe_scan_kernel((const int*)ids, S, E, k, MOE_BM, P, counts, offs, gather, inv); });
+    if (xg) emu::launch(dim3(P), dim3(256), [=] { moe_gather_kernel((const bf16_t*)x, ldx, (const int*)gather, (const float*)rstd, D, (bf16_t*)xg, rn_g); });
+    return 0;
+}
+extern "C" int32_t vl2_moe_gemm(const void* A, int32_t lda, const void* W, int64_t w_stride, int32_t ldw, void* C, int32_t ldc, const float* row_norm,
+                                float eps, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t P, int32_t N, int32_t K,
+                                int32_t flags, void*) {
+    if (!A || !W || !C || !counts || !offs || S <= 0 || k <= 0 || E <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemm: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemm: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (N % GEMM_BN || K % 64 || lda % 8 || ldw % 8 || ldc % 8 || w_stride % 8 || lda < K || ldw < K || w_stride < (int64_t)N * ldw ||
+        !EMU_ALIGNED16(A) || !EMU_ALIGNED16(W) || !EMU_ALIGNED16(C) || (row_norm && (((uintptr_t)row_norm) & 7)))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm: need N%%%d==0, K%%64==0, 16-byte aligned rows, w_stride >= N*ldw (N=%d K=%d)", GEMM_BN, N, K);
+    if (!moe_rows_ok(S, k, E, P)) return fail(VL2_E_SHAPE, "vl2_moe_gemm: P=%d must be a multiple of %d and >= S*k + E*%d", P, MOE_BM, MOE_BM - 1);
+    if ((int64_t)(GEMM_BM - 1) * lda + K >= ((int64_t)1 << 30) || (int64_t)(GEMM_BN - 1) * ldw + K >= ((int64_t)1 << 30))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm: a tile's rows exceed the kernels' 32-bit buffer offsets");
+    const bool sw = flags & VL2_GEMM_SWIGLU;
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemm: flags other than VL2_GEMM_SWIGLU not built");
+    if (sw && N % 64) return fail(VL2_E_SHAPE, "vl2_moe_gemm: SWIGLU needs N%%64==0");
+    MoeGemmArgs q{};
+    GemmArgs& a = q.g;
+    a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = C;
+    a.M = P; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldc = ldc;
+    a.stats_out_np = N / 64; a.stats_in_np = K / 64; a.idx_ld = P;
+    if (row_norm) { a.norm = VL2_NORM_RMS; a.norm_eps = eps; a.row_norm = row_norm; }
+    q.offs = offs; q.counts = counts; q.w_stride = w_stride; q.E = E; q.rt_cap = P / MOE_BM;
+    const dim3 grid((unsigned)(q.rt_cap * (N / GEMM_BN)));
+    if (sw) emu::launch(grid, dim3(512), [=] { moe_gemm_kernel<true>(q); });
+    else emu::launch(grid, dim3(512), [=] { moe_gemm_kernel<false>(q); });
+    return 0;
+}
+extern "C" int32_t vl2_moe_combine(const void* x1, int32_t ldx1, const void* y, int32_t ldy, const int32_t* inv, const float* wts, int32_t S, int32_t k,
+                                   int32_t D, float eps, void* out, int32_t ldo, float* row_norm, void*) {
+    if (!x1 || !y || !inv || !wts || !out || S <= 0 || k <= 0 || D <= 0) return fail(VL2_E_BADARG, "vl2_moe_combine: null pointer or empty shape");
+    if (k > MOE_MAX_K) return fail(VL2_E_UNSUPP, "vl2_moe_combine: k <= %d", MOE_MAX_K);
+    if (D % 8 || ldx1 % 8 || ldy % 8 || ldo % 8 || ldx1 < D || ldy < D || ldo < D || !EMU_ALIGNED16(x1) || !EMU_ALIGNED16(y) || !EMU_ALIGNED16(out) ||
+        (row_norm && (((uintptr_t)row_norm) & 7)))
+        return fail(VL2_E_SHAPE, "vl2_moe_combine: need D%%8==0, ldx1 / ldy / ldo >= D and 16-byte aligned rows (D=%d)", D);
+    emu::launch(dim3(S), dim3(256), [=] { moe_combine_kernel((const bf16_t*)x1, ldx1, (const bf16_t*)y, ldy, (const int*)inv, wts, k, D, eps, (bf16_t*)out, ldo, row_norm); });
+    return 0;
+}
+extern "C" int32_t vl2_moe_route_gemv(const void* x, const float* wr, int32_t D, int32_t E, int32_t k, float eps, int32_t* ids, float* wts, float* logits,
+                                      void*) {
+    if (!x || !wr || !ids || !wts || D <= 0 || E <= 0 || k <= 0) return fail(VL2_E_BADARG, "vl2_moe_route_gemv: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_route_gemv: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (D % 8 || !EMU_ALIGNED16(x) || !EMU_ALIGNED16(wr)) return fail(VL2_E_SHAPE, "vl2_moe_route_gemv: need D%%8==0 and 16-byte aligned rows");
+    emu::launch(dim3(1), dim3(256), [=] { moe_router_kernel((const bf16_t*)x, D, wr, 1, D, E, k, eps, ids, wts, (float*)nullptr, logits); });
+    return 0;
+}
+template <class F> static void emu_moe_down(int k, F f) {
+    if (k == 1) f(std::integral_constant<int, 1>()); else if (k == 2) f(std::integral_constant<int, 2>());
+    else if (k == 3) f(std::integral_constant<int, 3>()); else f(std::integral_constant<int, 4>());
+}
+extern "C" int32_t vl2_moe_gemv(const void* W, int64_t w_stride, int32_t ldw, const void* x, const int32_t* ids, const float* wts, const void* res,
+                                void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void*) {
+    if (!W || !x || !ids || !y || E <= 0 || k <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemv: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemv: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (K % 8 || ldw % 8 || ldw < K || w_stride < (int64_t)N * ldw || !EMU_ALIGNED16(W) || !EMU_ALIGNED16(x) || !EMU_ALIGNED16(y))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemv: need K%%8==0, 16-byte aligned rows, w_stride >= N*ldw");
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemv: flags other than VL2_GEMM_SWIGLU not built");
+    if (flags & VL2_GEMM_SWIGLU) {
+        if (N % 64 || K > 32704 || wts || res) return fail(VL2_E_SHAPE, "vl2_moe_gemv: SWIGLU needs N%%64==0, K<=32704 and no wts / res");
+        GemvArgs a{(const bf16_t*)W, (const bf16_t*)x, nullptr, nullptr, y, N, K, ldw, eps, nullptr, 0, 0, 0, 1};
+        emu::launch(dim3((N / 2 + 3) / 4, k), dim3(256), [=] { moe_gemv_gu_kernel(a, (const int*)ids, (long long)w_stride, N / 2); });
+        return 0;
+    }
+    if (!wts) return fail(VL2_E_BADARG, "vl2_moe_gemv: the down form needs the routing weights");
+    const size_t lds = (size_t)k * K * 2;
+    if (lds > 160 * 1024) return fail(VL2_E_SHAPE, "vl2_moe_gemv: k * K * 2 bytes of activations must fit the LDS (k=%d K=%d)", k, K);
+    emu_moe_down(k, [=](auto ks) {
+        emu::launch(dim3((N + 3) / 4), dim3(256), [=] { moe_gemv_down_kernel<decltype(ks)::value>((const bf16_t*)W, (long long)w_stride, ldw, (const bf16_t*)x, (const int*)ids, wts,
+                                                                                                    (const bf16_t*)res, (bf16_t*)y, N, K); });
+    });
+    return 0;
+}
+extern "C" int32_t vl2_moe_route_rows(const void* x, int32_t ldx, const float* wr, int32_t S, int32_t D, int32_t E, int32_t k, float eps, int32_t* ids,
+                                      float* wts, float* logits, int32_t* counts, int32_t* offs, int32_t* gather, int32_t* inv, void*) {
+    if (!x || !wr || !ids || !wts || S <= 0 || D <= 0 || E <= 0 || k <= 0) return fail(VL2_E_BADARG, "vl2_moe_route_rows: null pointer or empty shape");
+    const bool tables = counts || offs || gather || inv;
+    if (tables && (!counts || !offs || !gather || !inv)) return fail(VL2_E_BADARG, "vl2_moe_route_rows: counts / offs / gather / inv come together or not at all");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E)
+        return fail(VL2_E_UNSUPP, "vl2_moe_route_rows: need E <= %d and 1 <= k <= min(E, %d) (E=%d k=%d)", MOE_MAX_E, MOE_MAX_K, E, k);
+    if ((int64_t)S * k > MOE_SCAN_MAX) return fail(VL2_E_UNSUPP, "vl2_moe_route_rows: S * k <= %d (S=%d k=%d)", MOE_SCAN_MAX, S, k);
+    if (D % 8 || ldx % 8 || ldx < D || !EMU_ALIGNED16(x) || !EMU_ALIGNED16(wr))
+        return fail(VL2_E_SHAPE, "vl2_moe_route_rows: need D%%8==0, ldx>=D and 16-byte aligned rows (D=%d ldx=%d)", D, ldx);
+    emu::launch(dim3((S + 3) / 4), dim3(256), [=] { moe_router_kernel((const bf16_t*)x, ldx, wr, S, D, E, k, eps, ids, wts, (float*)nullptr, logits); });
+    if (tables) emu::launch(dim3(1), dim3(1024), [=] { moe_scan_kernel((const int*)ids, S, E, k, 1, S * k, counts, offs, gather, inv); });
+    return 0;
+}
+// the K split of the grouped skinny GEMM: skinny_plan's for (N, K), never shrunk; the staged rows (mt) from S -- the product's plan as it stands
+static int moe_skinny_plan(int S, int N, int K, SkinnyPlan& pl) { return skinny_plan(S, N, K, INT64_MAX, false, pl); }
+extern "C" int64_t vl2_moe_gemm_skinny_part_bytes(int32_t S, int32_t k, int32_t N, int32_t K) {
+    SkinnyPlan pl;
+    if (S <= 0 || S > 64 || k <= 0 || k > MOE_MAX_K || N <= 0 || K <= 0 || N % 64 || K % 32 || moe_skinny_plan(S, N, K, pl) != SKINNY_PLAN_OK) return -1;
+    return (int64_t)pl.ks * S * k * N * 4;
+}
+extern "C" int32_t vl2_moe_gemm_skinny(const void* A, int32_t lda, int32_t a_rows, const int32_t* rowmap, const void* W, int64_t w_stride, int32_t ldw,
+                                       void* C, int32_t ldc, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t N,
+                                       int32_t K, int32_t flags, void* part, int64_t part_bytes, void*) {
+    if (!A || !W || !C || !counts || !offs || S <= 0 || k <= 0 || E <= 0 || N <= 0 || K <= 0 || a_rows <= 0)
+        return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_skinny: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (S > 64) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: S=%d tokens, need S<=64 (vl2_moe_gemm beyond)", S);
+    const bool sw = flags & VL2_GEMM_SWIGLU;
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_skinny: flags other than VL2_GEMM_SWIGLU not built");
+    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
+    if (K % 32) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: need K%%32==0 (K=%d)", K);
+    const int R = S * k;
+    if (lda % 8 || ldw % 8 || ldc % 4 || lda < K || ldw < K || w_stride % 8 || w_stride < (int64_t)N * ldw || ldc < (sw ? N / 2 : N) ||
+        !EMU_ALIGNED16(A) || !EMU_ALIGNED16(W) || (((uintptr_t)C) & 7))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: need 16-byte aligned rows, lda%%8==0, ldw%%8==0, ldc%%4==0, lda / ldw >= K, w_stride >= N*ldw");
+    if (a_rows < (rowmap ? S : R)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: A has %d rows, need %d", a_rows, rowmap ? S : R);
+    if (!part || !EMU_ALIGNED16(part) || part_bytes <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny: needs a 16-byte aligned buffer of fp32 partial sums");
+    SkinnyPlan pl;
+    if (moe_skinny_plan(S, N, K, pl) != SKINNY_PLAN_OK) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny: no K chunking for K=%d", K);
+    const int64_t need = (int64_t)pl.ks * R * N * 4;
+    if (need > part_bytes)
+        return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny: partial buffer too small (%lld bytes, need %lld: the K split is never shrunk)", (long long)part_bytes, (long long)need);
+    MoeSkinnyArgs q{};
+    q.g = SkinnyArgs{(const bf16_t*)A, (const bf16_t*)W, (float*)part, S, N, K, lda, ldw, pl.kslice, pl.kchunk};
+    q.counts = counts; q.offs = offs; q.rowmap = rowmap; q.w_stride = w_stride; q.R = R; q.a_rows = a_rows;
+    const dim3 gk(N / 64, pl.ks, E), b(256);
+    if (pl.mt == 1) emu::launch(gk, b, [=] { moe_skinny_kernel<1>(q); });
+    else if (pl.mt == 2) emu::launch(gk, b, [=] { moe_skinny_kernel<2>(q); });
+    else emu::launch(gk, b, [=] { moe_skinny_kernel<4>(q); });
+    SkinnyReduceArgs r{(const float*)part, C, nullptr, nullptr, R, R, N, pl.ks, ldc, 0, nullptr};
+    const dim3 g((R * ((sw ? N / 2 : N) / 4) + 255) / 256);
+    if (sw) emu::launch(g, b, [=] { skinny_reduce_kernel<true, false, false>(r); });
+    else emu::launch(g, b, [=] { skinny_reduce_kernel<false, false, false>(r); });
+    return 0;
+}
+extern "C" int32_t vl2_moe_gemv_batched(const void* W, int64_t w_stride, int32_t ldw, const void* x, int32_t ldx, const int32_t* ids, const float* wts,
+                                        const void* res, int32_t ldres, void* y, int32_t ldy, int32_t S, int32_t E, int32_t k, int32_t N, int32_t K,
+                                        float eps, int32_t flags, void*) {
+    if (!W || !x || !ids || !y || S <= 0 || E <= 0 || k <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemv_batched: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemv_batched: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (S > 65535) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: S=%d tokens exceed the grid", S);
+    if (K % 8 || ldw % 8 || ldw < K || w_stride < (int64_t)N * ldw || ldx % 8 || ldx < K || !EMU_ALIGNED16(W) || !EMU_ALIGNED16(x) || !EMU_ALIGNED16(y))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: need K%%8==0, 16-byte aligned rows, ldw / ldx >= K, w_stride >= N*ldw");
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemv_batched: flags other than VL2_GEMM_SWIGLU not built");
+    if (flags & VL2_GEMM_SWIGLU) {
+        if (N % 64 || K > 32704 || wts || res || ldy < N / 2) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: SWIGLU needs N%%64==0, K<=32704, ldy >= N/2 and no wts / res");
+        GemvArgs a{(const bf16_t*)W, (const bf16_t*)x, nullptr, nullptr, y, N, K, ldw, eps, nullptr, 0, 0, 0, 1};
+        emu::launch(dim3((N / 2 + 3) / 4, k, S), dim3(256), [=] { moe_gemv_gu_rows_kernel(a, (const int*)ids, (long long)w_stride, ldy, ldx); });
+        return 0;
+    }
+    if (!wts) return fail(VL2_E_BADARG, "vl2_moe_gemv_batched: the down form needs the routing weights");
+    if (ldx != K) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: the down form reads the SwiGLU rows [S * k, K] without a gap (ldx=%d K=%d)", ldx, K);
+    if (ldy < N || (res && ldres < N)) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: need ldy / ldres >= N (N=%d)", N);
+    const size_t lds = (size_t)k * K * 2;
+    if (lds > 160 * 1024) return fail(VL2_E_SHAPE, "vl2_moe_gemv_batched: k * K * 2 bytes of activations must fit the LDS (k=%d K=%d)", k, K);
+    emu_moe_down(k, [=](auto ks) {
+        emu::launch(dim3((N + 3) / 4, S), dim3(256), [=] { moe_gemv_down_rows_kernel<decltype(ks)::value>((const bf16_t*)W, (long long)w_stride, ldw, (const bf16_t*)x, (const int*)ids, wts,
+                                                                                                            (const bf16_t*)res, ldres, (bf16_t*)y, ldy, N, K); });
+    });
+    return 0;
 }
 #include "vl2_stage.inc"

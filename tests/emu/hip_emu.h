@@ -264,6 +264,17 @@ inline bool wave_all(bool pred) {
     wave_sync();
     return r;
 }
+// __ballot: a wave rendezvous like the shuffles -- bit l of the result = lane l's predicate (every lane of the wave takes part)
+inline unsigned long long wave_ballot(bool pred) {
+    Wave& w = waves[cur->wave];
+    w.scratch[cur->lane][0] = pred ? 1 : 0;
+    wave_sync();
+    unsigned long long r = 0ull;
+    for (int i = 0; i < 64; ++i)
+        if (w.scratch[i][0]) r |= 1ull << i;
+    wave_sync();
+    return r;
+}
 // v_mov_b32_dpp with row_mask = bank_mask = 0xf and bound_ctrl: lane l reads `src` of the lane the control selects inside its row of 16
 // lanes.  Controls built: quad_perm (0x00-0xFF), row_half_mirror (0x141), row_mirror (0x140).
 template <class T> inline T shfl_idx(T v, int src);
@@ -343,6 +354,8 @@ inline void buffer_load_lds(Rsrc r, void* lds, unsigned size, unsigned voff, uns
 #define __builtin_nontemporal_load(p) (*(p))
 #define __builtin_nontemporal_store(v, p) (*(p) = (v))
 #define __all(p) emu::wave_all(p)
+#define __ballot(p) emu::wave_ballot(p)
+#define __popcll(x) __builtin_popcountll(x)
 #define __shfl_xor(v, m) emu::shfl_idx((v), emu::cur->lane ^ (m))
 #define __shfl_down(v, d) emu::shfl_idx((v), (emu::cur->lane + (d)) > 63 ? emu::cur->lane : emu::cur->lane + (d))
 #define __shfl(v, s) emu::shfl_idx((v), (s))
@@ -350,6 +363,7 @@ inline void buffer_load_lds(Rsrc r, void* lds, unsigned size, unsigned voff, uns
 #define __builtin_amdgcn_exp2f(x) exp2f(x)
 #define __fdividef(a, b) ((a) / (b))
 #define __frcp_rn(x) (1.0f / (x))
+#define __builtin_amdgcn_rcpf(x) (1.0f / (x))
 #define VL2_EMU 1
 // v_permlane32_swap_b32 vdst, src (k_gemm.h gemm_store_tr): lanes 32-63 of vdst trade places with lanes 0-31 of src
 template <class T> static inline void emu_permlane32_swap(T& vdst, T& src) {

@@ -43,6 +43,17 @@ __device__ __forceinline__ void moe_argmax_pair(float& v, int& i) {
     }
 }
 
+// a / b for the renormalised routing weights.  The library is built with -ffast-math, which turns `a / b` into a * rcp(b): p / p could then be
+// 1 - 2^-24 and p / (2 p) one step off 0.5, where MixtralTopKRouter's top_k_weights / sum gives exactly 1 for k = 1 and exactly 1 / k for k tied
+// experts.  One residual step on the hardware reciprocal is independent of the build's flags: q = a rcp(b), r = a - b q (exact in the fma),
+// q + r rcp(b).  For a = b and for b = k a with k a power of two the correction lands on 1 resp. 1 / k exactly (the error left is ~2^-47).
+__device__ __forceinline__ float moe_div(float a, float b) {
+#pragma clang fp reassociate(off)
+    const float r = __builtin_amdgcn_rcpf(b);
+    const float q = a * r;
+    return __builtin_fmaf(__builtin_fmaf(-b, q, a), r, q);
+}
+
 // grid = ceil(S / 4), block 256: one wave per token.  x [S][ldx], wr [E][D] fp32 (router rows times the norm weight: the product of two
 // 16-bit numbers is exact in fp32, so folding the norm costs the router no rounding -- a rounded fold moves logits by ~1e-3 relative and
 // flips top-k decisions whose margin is a few 1e-3).  Outputs ids / wts [S][k], rstd [S]
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(256) void moe_router_kernel(const bf16_t* __restric
         for (int j = 0; j < MOE_MAX_K; ++j)
             if (j < k) {
                 ids[(size_t)t * k + j] = sel_i[j];
-                wts[(size_t)t * k + j] = sel_v[j] / sum;
+                wts[(size_t)t * k + j] = moe_div(sel_v[j], sum);
             }
         if (rstd_out) rstd_out[t] = rstd;
     }
