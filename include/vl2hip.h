@@ -637,6 +637,28 @@ int32_t vl2_moe_gemv_batched(const void* W, int64_t w_stride, int32_t ldw, const
                              const void* res, int32_t ldres, void* y, int32_t ldy, int32_t S, int32_t E, int32_t k, int32_t N, int32_t K,
                              float eps, int32_t flags, void* stream);
 
+/* ---- fp8 expert weights for the MoE decode step (csrc/k_moe_fp8.h; W8A16, an OPTIONAL arithmetic).  q [E, N, ldq] = OCP e4m3fn bytes of the
+ * expert stack, expert e at q + e * q_stride bytes; scale [E, N] fp32 = one power-of-two scale per expert and output row, expert e at
+ * scale + e * s_stride floats (vl2_pack_quant_fp8 on the [E * N, K] view makes both).  The three calls mirror their 16-bit namesakes with
+ * q / q_stride / ldq / scale / s_stride in place of W / w_stride / ldw.  K % 16 == 0 (32 for the skinny form), K <= 32704. */
+/* vl2_moe_gemv on fp8 experts.  VL2_GEMM_SWIGLU (N % 64 == 0): slot j is bit for bit vl2_gemv_fp8(SWIGLU | RMS_PLAIN) on expert ids[j].
+ * flags 0 (any N; k * K * 2 bytes must fit the LDS): y[n] = bf16(res[n] + o), o = fma(wts[j], d_j, o) in slot order from 0, d_j bit for bit
+ * vl2_gemv_fp8(VL2_GEMM_OUT_F32)[n] on expert ids[j] and row x[j]. */
+int32_t vl2_moe_gemv_fp8(const void* q, int64_t q_stride, int32_t ldq, const float* scale, int64_t s_stride, const void* x, const int32_t* ids,
+                         const float* wts, const void* res, void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags,
+                         void* stream);
+/* vl2_moe_gemv_batched on fp8 experts: a token's rows are bit for bit vl2_moe_gemv_fp8's. */
+int32_t vl2_moe_gemv_batched_fp8(const void* q, int64_t q_stride, int32_t ldq, const float* scale, int64_t s_stride, const void* x, int32_t ldx,
+                                 const int32_t* ids, const float* wts, const void* res, int32_t ldres, void* y, int32_t ldy, int32_t S,
+                                 int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream);
+/* vl2_moe_gemm_skinny on fp8 experts, S <= 64: a permuted row is bit for bit vl2_gemm_skinny_fp8 on that one row with its expert's bytes and
+ * scales (hence vl2_moe_gemm_skinny on the dequantised stack).  part as for vl2_moe_gemm_skinny (vl2_moe_gemm_skinny_part_bytes).  Rows of C
+ * that no expert owns are not written; an expert without rows reads nothing. */
+int32_t vl2_moe_gemm_skinny_fp8(const void* A, int32_t lda, int32_t a_rows, const int32_t* rowmap, const void* q, int64_t q_stride, int32_t ldq,
+                                const float* scale, int64_t s_stride, void* C, int32_t ldc, const int32_t* counts, const int32_t* offs,
+                                int32_t S, int32_t k, int32_t E, int32_t N, int32_t K, int32_t flags, void* part, int64_t part_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

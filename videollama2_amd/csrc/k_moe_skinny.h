@@ -17,19 +17,23 @@
 #include "k_moe.h"
 #include "k_skinny.h"
 
-struct MoeSkinnyArgs {
-    SkinnyArgs g;             // A [a_rows, lda], W = expert 0, part [KS][R][N], M unused, N, K, lda, ldw, kslice, kchunk
+// (GA = the weight format's argument struct, k_skinny.h: SkinnyArgs here, Skinny8Args for the fp8 expert weights of k_moe_fp8.h)
+template <class GA>
+struct MoeSkinnyArgsT {
+    GA g;                     // A [a_rows, lda], W = expert 0, part [KS][R][N], M unused, N, K, lda, ldw, kslice, kchunk
     const int* counts;        // [E]
     const int* offs;          // [E + 1]
     const int* rowmap;        // [R] permuted row -> row of A, or null (A holds the permuted rows)
     long long w_stride;
     int R, a_rows;            // permuted rows (nb * k), rows of A
 };
+typedef MoeSkinnyArgsT<SkinnyArgs> MoeSkinnyArgs;
 
-template <int MT>
-__global__ __launch_bounds__(256) void moe_skinny_kernel(MoeSkinnyArgs q) {
+// WF = the weight-format policy of gemm_skinny_body (k_skinny.h); WF::at_expert moves the arguments to expert e's matrix
+template <int MT, class WF = SkinnyWBf16>
+__global__ __launch_bounds__(256) void moe_skinny_kernel(MoeSkinnyArgsT<typename WF::Args> q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vl2_smem[];
-    constexpr int Mp = 16 * MT, NL = SkinnyWBf16::NL;
+    constexpr int Mp = 16 * MT, NL = WF::NL;
     const int e = blockIdx.z;
     const int row0 = __builtin_amdgcn_readfirstlane(q.offs[e]);
     int cnt = __builtin_amdgcn_readfirstlane(q.counts[e]);
@@ -38,15 +42,15 @@ __global__ __launch_bounds__(256) void moe_skinny_kernel(MoeSkinnyArgs q) {
     if (row0 < 0 || row0 > q.R) return;
     if (cnt > q.R - row0) cnt = q.R - row0;
     if (cnt <= 0) return;                                  // an idle expert: no weight load
-    SkinnyArgs p = q.g;
-    p.W = q.g.W + (size_t)e * q.w_stride;
+    typename WF::Args p = q.g;
+    WF::at_expert(p, e, q.w_stride);
     bf16_t* xs = (bf16_t*)vl2_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.x * 64 + wave * 16;
     const int k0 = blockIdx.y * p.kslice;
     const int pitch = p.kchunk + 8;
     const int l15 = lane & 15, lg = lane >> 4;
-    const SkinnyWBf16 w(p, n0 + l15, k0, lg);
+    const WF w(p, n0 + l15, k0, lg);
     const int live = (cnt + 15) & ~15;                     // fragment rows that an MFMA reads
 
     f32x4v acc[MT];
@@ -56,7 +60,7 @@ __global__ __launch_bounds__(256) void moe_skinny_kernel(MoeSkinnyArgs q) {
     const int cvec = p.kchunk >> 3;
     for (int kc = 0; kc < p.kslice; kc += p.kchunk) {
         const int nstep = p.kchunk >> 5;
-        SkinnyWBf16::word wv[NL];
+        typename WF::word wv[NL];
 #pragma unroll
         for (int i = 0; i < NL; ++i)
             if (i < nstep) wv[i] = w.load(kc, i);
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(256) void moe_skinny_kernel(MoeSkinnyArgs q) {
 #pragma unroll
             for (int i = 0; i < NL; ++i) {
                 if (s0 + i < nstep) {
-                    const bf16x8 bfrag = SkinnyWBf16::frag(wv[i]);
+                    const bf16x8 bfrag = WF::frag(wv[i]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         if (m * 16 < cnt) {

@@ -35,6 +35,8 @@ struct SkinnyWBf16 {
     __device__ __forceinline__ SkinnyWBf16(const Args& p, int n, int k0, int lg) : wrow(p.W + (size_t)n * p.ldw + k0 + lg * 8) {}
     __device__ __forceinline__ word load(int kc, int s) const { return __builtin_nontemporal_load((const u32x4*)(wrow + kc + s * 32)); }
     static __device__ __forceinline__ bf16x8 frag(word w) { return __builtin_bit_cast(bf16x8, w); }
+    // the grouped form (k_moe_skinny.h): the arguments of expert e of a stack whose matrices lie `stride` elements apart
+    static __device__ __forceinline__ void at_expert(Args& p, int e, long long stride) { p.W += (size_t)e * stride; }
 };
 
 // THE skinny-M body of every weight format: grid = (N/64, KS), block 256; dynamic LDS = Mp * (kchunk + 8) * 2 bytes.  The grid, the K
@@ -113,13 +115,9 @@ struct SkinnyReduceArgs {
 
 // one thread per 4 consecutive output columns of one row; SWIGLU: W packed in 64-row blocks {32 gate, 32 up}.  SCALED (the fp8 weights of
 // gemm_skinny_fp8_kernel): the ordered sum of GEMM column n is multiplied by scale[n] before the epilogue -- gate and up by their own rows'.
-template <bool SWIGLU, bool OUT_F32, bool SCALED = false>
-__global__ __launch_bounds__(256) void skinny_reduce_kernel(SkinnyReduceArgs p) {
-    const int ncol = SWIGLU ? p.N / 2 : p.N;             // output columns
-    const int per_row = ncol >> 2;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.M * per_row) return;
-    const int m = e / per_row, c = (e - m * per_row) * 4;
+// (the body takes the row, the output column and the scale row so that k_moe_fp8.h can run it with the scales of the row's expert)
+template <bool SWIGLU, bool OUT_F32, bool SCALED>
+__device__ __forceinline__ void skinny_reduce_body(const SkinnyReduceArgs& p, int m, int c, const float* __restrict__ scale) {
     const int n = SWIGLU ? (c >> 5) * 64 + (c & 31) : c;  // GEMM column of the (gate) value
     f32x4v g = f32x4v{0.f, 0.f, 0.f, 0.f}, u = f32x4v{0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < p.KS; ++ks) {
@@ -136,8 +134,8 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(SkinnyReduceArgs p) 
     if (SCALED) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            g[j] *= p.scale[n + j];
-            if (SWIGLU) u[j] *= p.scale[n + 32 + j];
+            g[j] *= scale[n + j];
+            if (SWIGLU) u[j] *= scale[n + 32 + j];
         }
     }
     float o[4];
@@ -155,4 +153,14 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(SkinnyReduceArgs p) 
         w[1] = pack2bf(o[2], o[3]);
         *(u32x2*)((bf16_t*)p.C + (size_t)m * p.ldc + c) = w;
     }
+}
+
+template <bool SWIGLU, bool OUT_F32, bool SCALED = false>
+__global__ __launch_bounds__(256) void skinny_reduce_kernel(SkinnyReduceArgs p) {
+    const int ncol = SWIGLU ? p.N / 2 : p.N;             // output columns
+    const int per_row = ncol >> 2;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= p.M * per_row) return;
+    const int m = e / per_row, c = (e - m * per_row) * 4;
+    skinny_reduce_body<SWIGLU, OUT_F32, SCALED>(p, m, c, p.scale);
 }

@@ -1130,7 +1130,8 @@ class HipMixtralDecoder(HipMistralDecoder):
     router, token grouping, grouped expert GEMMs and combine on csrc/k_moe.h.  Runs operator by operator (the stage calls are
     dense-only); every routing table stays on the device, so the prefill and the decode step both capture into graphs.
     Single GPU, 16-bit weights: tensor parallelism and fp8 weights raise NotImplementedError, and so does batched / continuous decoding
-    until `enable_moe_batch()` switches it on."""
+    until `enable_moe_batch()` switches it on.  `enable_moe_fp8()` is this decoder's own fp8 switch: the decode
+    step's expert products on e4m3fn copies of the expert stacks, everything else 16-bit."""
 
     def __init__(self, cfg, state_dict, device="cuda", max_seq_len=4096, n_layers=None, tp_group=None, tp_shard=None, tp_local=None):
         if tp_group is not None or tp_shard is not None or tp_local is not None:
@@ -1193,6 +1194,35 @@ class HipMixtralDecoder(HipMistralDecoder):
         self._bb = None
         return self
 
+    MOE_FP8_ROWS = 64       # the most sequences of a batched step while enable_moe_fp8 is on: the grouped skinny-M GEMM's limit (no tiled W8A16
+    #                         grouped GEMM is built, and the 16-bit tiled form would change a request's arithmetic with the batch size)
+
+    @property
+    def moe_fp8(self):
+        """Whether the decode step's expert products stream fp8 copies of the expert weights (enable_moe_fp8)."""
+        return getattr(self, "_moe_fp8", False)
+
+    @torch.no_grad()
+    def enable_moe_fp8(self, on=True):
+        """OPTIONAL arithmetic, never the default: every expert product of the decode step -- the solo step, and with
+        enable_moe_batch() the batched and continuous steps -- reads OCP e4m3fn copies of wgu [E, 2I, D] and wd [E, D, I] with one power-of-two
+        scale per expert and output row (ops.moe_quant_fp8, the quantiser of oracle/fp8_oracle.py); activations stay 16-bit, products and sums
+        fp32 (csrc/k_moe_fp8.h).  The prefill, the router, attention, RoPE, the KV cache, wqkv / wo and lm_head keep their 16-bit weights, so
+        `decode_format` stays "16bit" and enable_fp8_decode / enable_fp8_prefill / enable_mxfp4_decode keep refusing.  The copies are made
+        once, here (+45 GB beside the 93 GB of 16-bit weights for the 8x7B model at full depth; the prefill still reads the latter).
+        A batched step runs the fp8 rows kernels below MOE_GEMM_BATCH sequences and the fp8 grouped skinny-M GEMM from there to MOE_FP8_ROWS
+        = 64; more slots than that are refused (the 16-bit tiled form is never used while the switch is on).  Switching drops the captured
+        graphs and bumps cache_epoch; it is refused while a batcher holds requests in flight."""
+        busy = getattr(self, "_bb_busy", None)
+        if busy is not None and busy.in_flight():
+            raise RuntimeError("enable_moe_fp8: a ContinuousBatcher holds requests in flight on this decoder's slots: drain it (run()) first")
+        if on and getattr(self, "w8moe", None) is None:
+            self.w8moe = [dict(wgu=ops.moe_quant_fp8(lw["wgu"]), wd=ops.moe_quant_fp8(lw["wd"])) for lw in self.w["layers"]]
+        self._moe_fp8 = bool(on)
+        self._invalidate_graphs()
+        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
+        return self
+
     def prefill_batch(self, xs, caches, logits_out):
         if not getattr(self, "_moe_batch", False):
             raise NotImplementedError("MoE (mixtral) decoder: batched prefill not built")
@@ -1240,6 +1270,10 @@ class HipMixtralDecoder(HipMistralDecoder):
     def _ensure_batch(self, B, owner=None):
         if not getattr(self, "_moe_batch", False):
             raise NotImplementedError("MoE (mixtral) decoder: batched / continuous decoding not built")
+        if self.moe_fp8 and B > self.MOE_FP8_ROWS:
+            raise NotImplementedError(f"MoE (mixtral) decoder: fp8 expert weights are on (enable_moe_fp8): a batched step takes at most "
+                                      f"{self.MOE_FP8_ROWS} sequences, the grouped skinny-M GEMM's limit (no tiled W8A16 grouped GEMM is built); "
+                                      f"got {B}")
         bb = super()._ensure_batch(B, owner)
         if "moe" not in bb:
             bb["moe"] = self._moe_step_buffers(bb["B"])
@@ -1273,14 +1307,37 @@ class HipMixtralDecoder(HipMistralDecoder):
         experts (one launch); down GEMV of both (one launch, weighted, + residual) into x.  No host read: the step replays as a graph."""
         lw = self.w["layers"][li]
         if x.dim() == 2:
-            return self._token_block_batched(f, lw, o, x, x1)
+            return self._token_block_batched(f, lw, o, x, x1, li)
         ops.gemv(lw["wo"], o, res=x, out=x1)
         ops.moe_route_gemv(x1, lw["wr"], self.moe_ids, self.moe_wts, self.eps)
+        if self.moe_fp8:                         # the same two launches on the fp8 copies of the expert stacks (enable_moe_fp8)
+            w8 = self.w8moe[li]
+            ops.moe_gemv_fp8(*w8["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
+            ops.moe_gemv_fp8(*w8["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
+            return
         ops.moe_gemv(lw["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
         ops.moe_gemv(lw["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
 
+    def _token_block_batched_fp8(self, w8, lw, x, x1, nb, m, ids, wts):
+        """The MoE block of a batched step on the fp8 expert copies: the rows kernels below MOE_GEMM_BATCH (a row is bit for bit the solo fp8
+        step), the grouped skinny-M GEMM from there to MOE_FP8_ROWS (the solo fp8 step up to summation order)."""
+        k, R = self.k, nb * self.k
+        if nb > self.MOE_FP8_ROWS:
+            raise NotImplementedError(f"MoE (mixtral) decoder: fp8 expert weights are on (enable_moe_fp8): a batched step takes at most "
+                                      f"{self.MOE_FP8_ROWS} sequences, got {nb}")
+        if nb < self.MOE_GEMM_BATCH:
+            ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
+            ops.moe_gemv_batched_fp8(*w8["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])
+            ops.moe_gemv_batched_fp8(*w8["wd"], m["a"][:R], ids, wts=wts, res=x1, out=x)
+            return
+        t = dict(counts=m["counts"], offs=m["offs"], gather=m["gather"][:R], inv=m["inv"][:nb], wts=wts)
+        ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts, tables=t)
+        h = ops.rmsnorm(x1, self.w["ones"], self.eps, out=m["h"][:nb])              # (the norm weight is folded into wgu)
+        ops.moe_gemm_skinny_fp8(h, *w8["wgu"], t, nb, k, m["part"], rowmap=t["gather"], swiglu=True, out=m["a"][:R])
+        ops.moe_gemm_skinny_fp8(m["a"][:R], *w8["wd"], t, nb, k, m["part"], out=m["y"][:R])
+        ops.moe_combine(x1, m["y"][:R], t, self.eps, out=x)
 
-    def _token_block_batched(self, f, lw, o, x, x1):
+    def _token_block_batched(self, f, lw, o, x, x1, li=None):
         """The same for the nb rows of a batched step (enable_moe_batch), on the slot buffers' MoE tensors: x1 = x + o_proj(o) through the
         form, then one of three regimes by nb (class attributes MOE_GEMM_BATCH / MOE_SKINNY_ROWS).  No host read and, in the first two, no
         allocation: the step captures into one hipGraph per batch size."""
@@ -1288,7 +1345,9 @@ class HipMixtralDecoder(HipMistralDecoder):
         R = nb * k
         f.res(o, lw["wo"], x, out=x1)
         ids, wts = m["ids"][:nb], m["wts"][:nb]
-        if nb < self.MOE_GEMM_BATCH:             # the solo step's GEMVs, a token index in the grid: every (token, slot) pair streams its expert
+        if self.moe_fp8:                         # (enable_moe_fp8: the 16-bit regimes below are untouched with the switch off)
+            self._token_block_batched_fp8(self.w8moe[li], lw, x, x1, nb, m, ids, wts)
+        elif nb < self.MOE_GEMM_BATCH:             # the solo step's GEMVs, a token index in the grid: every (token, slot) pair streams its expert
             ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
             ops.moe_gemv_batched(lw["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])
             ops.moe_gemv_batched(lw["wd"], m["a"][:R], ids, wts=wts, res=x1, out=x)

@@ -1262,3 +1262,68 @@ def moe_gemv_batched(w, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=
     _lib.call("vl2_moe_gemv_batched", _p(w), w.stride(0), w.stride(1), _p(x), x.stride(0), _p(ids), _p(wts), _p(res),
               0 if res is None else res.stride(0), _p(out), out.stride(0), S, E, k, N, K, float(eps), GEMM_SWIGLU if swiglu else 0, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ fp8 expert weights of the MoE decode, csrc/k_moe_fp8.h
+def moe_quant_fp8(w):
+    """An expert stack w [E, N, K] (contiguous, 16-bit) -> (q uint8 [E, N, K] e4m3fn bytes, scale fp32 [E, N]: one power-of-two scale per expert
+    and output row): ONE vl2_pack_quant_fp8 call on the [E * N, K] view, so expert e is `quant_fp8(w[e])` bit for bit."""
+    _chk(w, _lib.elem_dtype(), "w")
+    E, N, K = w.shape
+    if not w.is_contiguous():
+        raise ValueError("moe_quant_fp8: the expert stack must be contiguous (it is quantised as its [E * N, K] view)")
+    q, sc = quant_fp8(w.view(E * N, K))
+    return q.view(E, N, K), sc.view(E, N)
+
+
+def _chk_moe8(who, q, scale):
+    _chk(q, torch.uint8, "q"); _chk(scale, torch.float32, "scale")
+    if q.dim() != 3 or scale.dim() != 2 or tuple(scale.shape) != tuple(q.shape[:2]) or q.stride(2) != 1 or scale.stride(1) != 1:
+        raise ValueError(f"{who}: need q [E, N, K] bytes and scale [E, N] (moe_quant_fp8), got {tuple(q.shape)} and {tuple(scale.shape)}")
+    return q.shape
+
+
+def moe_gemv_fp8(q, scale, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
+    """include/vl2hip.h vl2_moe_gemv_fp8: `moe_gemv` on the fp8 expert stack (q, scale) of `moe_quant_fp8`.  swiglu=True: slot j is bit for bit
+    gemv_fp8(q[ids[j]], scale[ids[j]], x, swiglu=True, rms_plain=True); else out = res + sum_j wts[j] * gemv_fp8(.., x[j], out_f32=True) as an fma
+    chain in slot order, rounded once."""
+    E, N, K = _chk_moe8("moe_gemv_fp8", q, scale)
+    _chk(x, _lib.elem_dtype(), "x"); _chk(res, _lib.elem_dtype(), "res"); _chk(wts, torch.float32, "wts")
+    k = ids.numel()
+    if out is None:
+        out = torch.empty((k, N // 2) if swiglu else (N,), dtype=_lib.elem_dtype(), device=q.device)
+    _lib.call("vl2_moe_gemv_fp8", _p(q), q.stride(0), q.stride(1), _p(scale), scale.stride(0), _p(x), _p(ids), _p(wts), _p(res), _p(out), E, k, N, K,
+              float(eps), GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
+
+
+def moe_gemv_batched_fp8(q, scale, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
+    """include/vl2hip.h vl2_moe_gemv_batched_fp8: `moe_gemv_fp8` for the S tokens of ids [S, k] in one launch; a token's rows are its bits."""
+    E, N, K = _chk_moe8("moe_gemv_batched_fp8", q, scale)
+    _chk(x, _lib.elem_dtype(), "x"); _chk(res, _lib.elem_dtype(), "res"); _chk(wts, torch.float32, "wts")
+    S, k = ids.shape
+    if x.shape[0] < (S if swiglu else S * k) or (res is not None and res.shape[0] < S) or (wts is not None and wts.numel() < S * k):
+        raise ValueError("moe_gemv_batched_fp8: x / res / wts are too short for the S tokens of ids")
+    if out is None:
+        out = torch.empty((S * k, N // 2) if swiglu else (S, N), dtype=_lib.elem_dtype(), device=q.device)
+    if out.shape[0] < (S * k if swiglu else S):
+        raise ValueError("moe_gemv_batched_fp8: out is too short for the S tokens of ids")
+    _lib.call("vl2_moe_gemv_batched_fp8", _p(q), q.stride(0), q.stride(1), _p(scale), scale.stride(0), _p(x), x.stride(0), _p(ids), _p(wts), _p(res),
+              0 if res is None else res.stride(0), _p(out), out.stride(0), S, E, k, N, K, float(eps), GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
+
+
+def moe_gemm_skinny_fp8(a, q, scale, tables, S, k, part, rowmap=None, swiglu=False, out=None):
+    """include/vl2hip.h vl2_moe_gemm_skinny_fp8: `moe_gemm_skinny` on the fp8 expert stack (q, scale): a permuted row is bit for bit
+    `gemm_skinny_fp8` on that one row with its expert's bytes and scales.  part: fp32 buffer of moe_skinny_part_bytes(S, k, N, K)."""
+    E, N, K = _chk_moe8("moe_gemm_skinny_fp8", q, scale)
+    _chk(a, _lib.elem_dtype(), "a"); _chk(part, torch.float32, "part")
+    R = S * k
+    if out is None:
+        out = torch.empty((R, N // 2 if swiglu else N), dtype=_lib.elem_dtype(), device=a.device)
+    if out.shape[0] < R or (rowmap is not None and rowmap.numel() < R) or tables["counts"].numel() < E or tables["offs"].numel() < E + 1:
+        raise ValueError("moe_gemm_skinny_fp8: out / rowmap / tables are too short for S * k rows and E experts")
+    _lib.call("vl2_moe_gemm_skinny_fp8", _p(a), a.stride(0), a.shape[0], _p(rowmap), _p(q), q.stride(0), q.stride(1), _p(scale), scale.stride(0),
+              _p(out), out.stride(0), _p(tables["counts"]), _p(tables["offs"]), S, k, E, N, K, GEMM_SWIGLU if swiglu else 0, _p(part),
+              part.numel() * 4, _stream())
+    return out
