@@ -659,6 +659,14 @@ int32_t vl2_moe_gemm_skinny_fp8(const void* A, int32_t lda, int32_t a_rows, cons
                                 int32_t S, int32_t k, int32_t E, int32_t N, int32_t K, int32_t flags, void* part, int64_t part_bytes,
                                 void* stream);
 
+/* ---- tiled W8A16 grouped GEMM on the fp8 expert stacks (csrc/k_moe_gemm8.h): vl2_moe_gemm with q / q_stride / ldq / scale / s_stride in place
+ * of W / w_stride / ldw, any number of tokens.  A permuted row is bit for bit vl2_moe_gemm on the dequantised stack q * scale (the k order of
+ * the 16 x 16 x 32 tile is the same and a power-of-two scale is exact).  N % 128 == 0, K % 64 == 0, ldq % 16 == 0, ldq >= K, q_stride % 16 == 0,
+ * q_stride >= N * ldq, q and scale 16-byte aligned, s_stride % 4 == 0, s_stride >= N; P as for vl2_moe_gemm.  flags: VL2_GEMM_SWIGLU only. */
+int32_t vl2_moe_gemm_fp8(const void* A, int32_t lda, const void* q, int64_t q_stride, int32_t ldq, const float* scale, int64_t s_stride, void* C,
+                         int32_t ldc, const float* row_norm, float eps, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k,
+                         int32_t E, int32_t P, int32_t N, int32_t K, int32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

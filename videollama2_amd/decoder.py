@@ -1194,16 +1194,30 @@ class HipMixtralDecoder(HipMistralDecoder):
         self._bb = None
         return self
 
-    MOE_FP8_ROWS = 64       # the most sequences of a batched step while enable_moe_fp8 is on: the grouped skinny-M GEMM's limit (no tiled W8A16
-    #                         grouped GEMM is built, and the 16-bit tiled form would change a request's arithmetic with the batch size)
+    MOE_FP8_ROWS = 64       # the most sequences of a batched step while enable_moe_fp8 is on WITHOUT tiled=True: the grouped skinny-M GEMM's
+    #                         limit (the 16-bit tiled form would change a request's arithmetic with the batch size; the tiled W8A16 grouped
+    #                         GEMM, csrc/k_moe_gemm8.h, serves any number of sequences behind enable_moe_fp8(tiled=True))
+    # With enable_moe_fp8(tiled=True): from this many sequences on the fp8 step runs the tiled W8A16 grouped GEMM (ops.moe_gemm_fp8), below it
+    # the fp8 grouped skinny-M GEMM.  The rule: the smallest measured size from which the tiled fp8 step is faster than the fp8 skinny step at
+    # that size and at every larger measured size by more than twice the spread of the 16-bit step timed twice; 65 if there is none (tiled then
+    # serves only what was refused before).  Measured (scripts/moe_fp8_tiled_bench.py, profiles/r23_moe_fp8_tiled_bench.jsonl, DESIGN.md 22d;
+    # ms per 8-layer step, skinny / tiled, spread <= 0.003 ms): 5: 3.37 / 3.26, 6: 3.58 / 3.37, 8: 3.85 / 3.51, 12: 4.27 / 3.70, 16: 4.58 / 3.80,
+    # 24: 5.28 / 4.01, 32: 5.59 / 4.17, 48: 6.76 / 4.51, 64: 7.29 / 4.80 -- the tiled form wins at every measured size, so the fp8 skinny form
+    # serves no size under tiled=True (the value is clamped to MOE_GEMM_BATCH: the rows kernels keep the sizes below it)
+    MOE_FP8_TILED_FROM = 5
 
     @property
     def moe_fp8(self):
         """Whether the decode step's expert products stream fp8 copies of the expert weights (enable_moe_fp8)."""
         return getattr(self, "_moe_fp8", False)
 
+    @property
+    def moe_fp8_tiled(self):
+        """Whether the batched fp8 step may run the tiled W8A16 grouped GEMM (enable_moe_fp8(tiled=True))."""
+        return getattr(self, "_moe_fp8_tiled", False)
+
     @torch.no_grad()
-    def enable_moe_fp8(self, on=True):
+    def enable_moe_fp8(self, on=True, tiled=False):
         """OPTIONAL arithmetic, never the default: every expert product of the decode step -- the solo step, and with
         enable_moe_batch() the batched and continuous steps -- reads OCP e4m3fn copies of wgu [E, 2I, D] and wd [E, D, I] with one power-of-two
         scale per expert and output row (ops.moe_quant_fp8, the quantiser of oracle/fp8_oracle.py); activations stay 16-bit, products and sums
@@ -1211,14 +1225,19 @@ class HipMixtralDecoder(HipMistralDecoder):
         `decode_format` stays "16bit" and enable_fp8_decode / enable_fp8_prefill / enable_mxfp4_decode keep refusing.  The copies are made
         once, here (+45 GB beside the 93 GB of 16-bit weights for the 8x7B model at full depth; the prefill still reads the latter).
         A batched step runs the fp8 rows kernels below MOE_GEMM_BATCH sequences and the fp8 grouped skinny-M GEMM from there to MOE_FP8_ROWS
-        = 64; more slots than that are refused (the 16-bit tiled form is never used while the switch is on).  Switching drops the captured
-        graphs and bumps cache_epoch; it is refused while a batcher holds requests in flight."""
+        = 64; more slots than that are refused (the 16-bit tiled form is never used while the switch is on).
+        tiled=True adds a third regime: from MOE_FP8_TILED_FROM sequences on, for any number of them, the prefill's
+        sparse block on the fp8 stacks -- ops.moe_route, the tiled W8A16 grouped GEMM ops.moe_gemm_fp8 (csrc/k_moe_gemm8.h) twice,
+        ops.moe_combine -- so more than 64 slots are admitted.  Both grouped forms are W8A16 on the same bytes: a request's arithmetic still
+        changes with the batch size by summation order only.
+        Switching `on` or `tiled` drops the captured graphs and bumps cache_epoch; it is refused while a batcher holds requests in flight."""
         busy = getattr(self, "_bb_busy", None)
         if busy is not None and busy.in_flight():
             raise RuntimeError("enable_moe_fp8: a ContinuousBatcher holds requests in flight on this decoder's slots: drain it (run()) first")
         if on and getattr(self, "w8moe", None) is None:
             self.w8moe = [dict(wgu=ops.moe_quant_fp8(lw["wgu"]), wd=ops.moe_quant_fp8(lw["wd"])) for lw in self.w["layers"]]
         self._moe_fp8 = bool(on)
+        self._moe_fp8_tiled = bool(on and tiled)
         self._invalidate_graphs()
         self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
         return self
@@ -1270,7 +1289,7 @@ class HipMixtralDecoder(HipMistralDecoder):
     def _ensure_batch(self, B, owner=None):
         if not getattr(self, "_moe_batch", False):
             raise NotImplementedError("MoE (mixtral) decoder: batched / continuous decoding not built")
-        if self.moe_fp8 and B > self.MOE_FP8_ROWS:
+        if self.moe_fp8 and not self.moe_fp8_tiled and B > self.MOE_FP8_ROWS:
             raise NotImplementedError(f"MoE (mixtral) decoder: fp8 expert weights are on (enable_moe_fp8): a batched step takes at most "
                                       f"{self.MOE_FP8_ROWS} sequences, the grouped skinny-M GEMM's limit (no tiled W8A16 grouped GEMM is built); "
                                       f"got {B}")
@@ -1320,8 +1339,15 @@ class HipMixtralDecoder(HipMistralDecoder):
 
     def _token_block_batched_fp8(self, w8, lw, x, x1, nb, m, ids, wts):
         """The MoE block of a batched step on the fp8 expert copies: the rows kernels below MOE_GEMM_BATCH (a row is bit for bit the solo fp8
-        step), the grouped skinny-M GEMM from there to MOE_FP8_ROWS (the solo fp8 step up to summation order)."""
+        step), the grouped skinny-M GEMM from there to MOE_FP8_ROWS (the solo fp8 step up to summation order); with enable_moe_fp8(tiled=True)
+        the tiled W8A16 grouped GEMM from MOE_FP8_TILED_FROM on, for any nb (the same, up to summation order).  Returns the (ids, wts) the
+        block routed with."""
         k, R = self.k, nb * self.k
+        if self.moe_fp8_tiled and nb >= max(self.MOE_FP8_TILED_FROM, self.MOE_GEMM_BATCH):
+            r = ops.moe_route(x1, lw["wr"], k, self.eps)    # the prefill's sparse block on the fp8 stacks (its tables are sized per call)
+            a = ops.moe_gemm_fp8(r["xg"], *w8["wgu"], r, nb, k, swiglu=True, row_norm=r["rn"], eps=self.eps)
+            ops.moe_combine(x1, ops.moe_gemm_fp8(a, *w8["wd"], r, nb, k), r, self.eps, out=x)
+            return r["ids"], r["wts"]
         if nb > self.MOE_FP8_ROWS:
             raise NotImplementedError(f"MoE (mixtral) decoder: fp8 expert weights are on (enable_moe_fp8): a batched step takes at most "
                                       f"{self.MOE_FP8_ROWS} sequences, got {nb}")
@@ -1329,13 +1355,14 @@ class HipMixtralDecoder(HipMistralDecoder):
             ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
             ops.moe_gemv_batched_fp8(*w8["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])
             ops.moe_gemv_batched_fp8(*w8["wd"], m["a"][:R], ids, wts=wts, res=x1, out=x)
-            return
+            return ids, wts
         t = dict(counts=m["counts"], offs=m["offs"], gather=m["gather"][:R], inv=m["inv"][:nb], wts=wts)
         ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts, tables=t)
         h = ops.rmsnorm(x1, self.w["ones"], self.eps, out=m["h"][:nb])              # (the norm weight is folded into wgu)
         ops.moe_gemm_skinny_fp8(h, *w8["wgu"], t, nb, k, m["part"], rowmap=t["gather"], swiglu=True, out=m["a"][:R])
         ops.moe_gemm_skinny_fp8(m["a"][:R], *w8["wd"], t, nb, k, m["part"], out=m["y"][:R])
         ops.moe_combine(x1, m["y"][:R], t, self.eps, out=x)
+        return ids, wts
 
     def _token_block_batched(self, f, lw, o, x, x1, li=None):
         """The same for the nb rows of a batched step (enable_moe_batch), on the slot buffers' MoE tensors: x1 = x + o_proj(o) through the
@@ -1346,7 +1373,7 @@ class HipMixtralDecoder(HipMistralDecoder):
         f.res(o, lw["wo"], x, out=x1)
         ids, wts = m["ids"][:nb], m["wts"][:nb]
         if self.moe_fp8:                         # (enable_moe_fp8: the 16-bit regimes below are untouched with the switch off)
-            self._token_block_batched_fp8(self.w8moe[li], lw, x, x1, nb, m, ids, wts)
+            ids, wts = self._token_block_batched_fp8(self.w8moe[li], lw, x, x1, nb, m, ids, wts)
         elif nb < self.MOE_GEMM_BATCH:             # the solo step's GEMVs, a token index in the grid: every (token, slot) pair streams its expert
             ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
             ops.moe_gemv_batched(lw["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])

@@ -444,14 +444,14 @@ class VideoLLaMA2Hip(nn.Module):
         self.decoder.enable_moe_batch(on)
         return self
 
-    def enable_moe_fp8(self, on=True):
+    def enable_moe_fp8(self, on=True, tiled=False):
         """OPTIONAL arithmetic, Mixtral only, never the default: the decode step's expert products stream fp8 (e4m3fn) copies of the expert
         weights with one power-of-two scale per expert and output row (`HipMixtralDecoder.enable_moe_fp8`).  The
         prefill, the router, attention, wqkv / wo and lm_head stay 16-bit; with enable_moe_batch() batches of up to 64 requests decode on
-        the same copies."""
+        the same copies, and with tiled=True (the tiled W8A16 grouped GEMM) batches of any size."""
         if not hasattr(self.decoder, "enable_moe_fp8"):
             raise NotImplementedError("enable_moe_fp8: the decoder is dense (it has no expert weights; enable_fp8_decode() is its fp8 switch)")
-        self.decoder.enable_moe_fp8(on)
+        self.decoder.enable_moe_fp8(on, tiled=tiled)
         return self
 
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None, reserve="whole"):

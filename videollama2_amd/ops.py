@@ -1327,3 +1327,18 @@ def moe_gemm_skinny_fp8(a, q, scale, tables, S, k, part, rowmap=None, swiglu=Fal
               _p(out), out.stride(0), _p(tables["counts"]), _p(tables["offs"]), S, k, E, N, K, GEMM_SWIGLU if swiglu else 0, _p(part),
               part.numel() * 4, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ tiled W8A16 grouped GEMM, csrc/k_moe_gemm8.h
+def moe_gemm_fp8(a, q, scale, route, S, k, swiglu=False, row_norm=None, eps=0.0, out=None):
+    """include/vl2hip.h vl2_moe_gemm_fp8: `moe_gemm` on the fp8 expert stack (q, scale) of `moe_quant_fp8`, any number of tokens: the grouped
+    GEMM over the permuted rows a [P, K] (route = moe_route's dict) -> [P, N] (swiglu [P, N/2]); rows of padding are left unwritten.  A row is
+    bit for bit `moe_gemm` on the dequantised stack q * scale."""
+    E, N, K = _chk_moe8("moe_gemm_fp8", q, scale)
+    _chk(a, _lib.elem_dtype(), "a"); _chk(row_norm, torch.float32, "row_norm")
+    P = a.shape[0]
+    if out is None:
+        out = torch.empty((P, N // 2 if swiglu else N), dtype=_lib.elem_dtype(), device=a.device)
+    _lib.call("vl2_moe_gemm_fp8", _p(a), a.stride(0), _p(q), q.stride(0), q.stride(1), _p(scale), scale.stride(0), _p(out), out.stride(0),
+              _p(row_norm), float(eps), _p(route["counts"]), _p(route["offs"]), S, k, E, P, N, K, GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
