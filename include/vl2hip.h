@@ -667,6 +667,30 @@ int32_t vl2_moe_gemm_fp8(const void* A, int32_t lda, const void* q, int64_t q_st
                          int32_t ldc, const float* row_norm, float eps, const int32_t* counts, const int32_t* offs, int32_t S, int32_t k,
                          int32_t E, int32_t P, int32_t N, int32_t K, int32_t flags, void* stream);
 
+/* ---- MXFP4 expert weights for the MoE decode step (csrc/k_moe_mxfp4.h; W4A16, an OPTIONAL arithmetic).  q [E, N, ldq] = bytes of two E2M1
+ * codes (k = 2j in bits 3:0), expert e at q + e * q_stride bytes; scale [E, N, lds] = E8M0 bytes, one per 32 k, expert e at scale +
+ * e * s_stride bytes (ONE vl2_pack_quant_mxfp4 call on the [E * N, K] view makes both).  The three calls mirror their 16-bit namesakes with
+ * q / q_stride / ldq / scale / s_stride / lds in place of W / w_stride / ldw.  K % 32 == 0, K <= 32704, ldq % 16 == 0, ldq >= K / 2,
+ * lds >= K / 32, q_stride % 16 == 0, q_stride >= N * ldq, s_stride >= N * lds.  No tiled W4A16 grouped GEMM is built: the skinny form
+ * (S <= 64) is the only grouped one. */
+/* vl2_moe_gemv on MXFP4 experts.  VL2_GEMM_SWIGLU (N % 64 == 0): slot j is bit for bit vl2_gemv_mxfp4(SWIGLU | RMS_PLAIN) on expert ids[j].
+ * flags 0 (any N; k * K * 2 bytes must fit the LDS): y[n] = elem(res[n] + o), o = fma(wts[j], d_j, o) in slot order from 0, d_j bit for bit
+ * vl2_gemv_mxfp4(VL2_GEMM_OUT_F32)[n] on expert ids[j] and row x[j]. */
+int32_t vl2_moe_gemv_mxfp4(const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride, int32_t lds, const void* x,
+                           const int32_t* ids, const float* wts, const void* res, void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps,
+                           int32_t flags, void* stream);
+/* vl2_moe_gemv_batched on MXFP4 experts: a token's rows are bit for bit vl2_moe_gemv_mxfp4's. */
+int32_t vl2_moe_gemv_batched_mxfp4(const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride, int32_t lds, const void* x,
+                                   int32_t ldx, const int32_t* ids, const float* wts, const void* res, int32_t ldres, void* y, int32_t ldy,
+                                   int32_t S, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream);
+/* vl2_moe_gemm_skinny on MXFP4 experts, S <= 64: a permuted row is bit for bit vl2_gemm_skinny_mxfp4 on that one row with its expert's bytes
+ * and scales (hence vl2_moe_gemm_skinny on the dequantised stack).  part as for vl2_moe_gemm_skinny (vl2_moe_gemm_skinny_part_bytes).  Rows
+ * of C that no expert owns are not written, neither are their partials; an expert without rows reads nothing. */
+int32_t vl2_moe_gemm_skinny_mxfp4(const void* A, int32_t lda, int32_t a_rows, const int32_t* rowmap, const void* q, int64_t q_stride, int32_t ldq,
+                                  const void* scale, int64_t s_stride, int32_t lds, void* C, int32_t ldc, const int32_t* counts,
+                                  const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t N, int32_t K, int32_t flags, void* part,
+                                  int64_t part_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,8 @@
 #include "k_moe.h"
 #include "k_skinny.h"
 
-// (GA = the weight format's argument struct, k_skinny.h: SkinnyArgs here, Skinny8Args for the fp8 expert weights of k_moe_fp8.h)
+// (GA = the weight format's argument struct, k_skinny.h: SkinnyArgs here, Skinny8Args for the fp8 expert weights of k_moe_fp8.h, Skinny4Args
+// for the MXFP4 expert weights of k_moe_mxfp4.h)
 template <class GA>
 struct MoeSkinnyArgsT {
     GA g;                     // A [a_rows, lda], W = expert 0, part [KS][R][N], M unused, N, K, lda, ldw, kslice, kchunk
@@ -26,6 +27,7 @@ struct MoeSkinnyArgsT {
     const int* rowmap;        // [R] permuted row -> row of A, or null (A holds the permuted rows)
     long long w_stride;
     int R, a_rows;            // permuted rows (nb * k), rows of A
+    long long s_stride;       // MXFP4 only: bytes between two experts' scale arrays (the 16-bit and fp8 policies ignore it)
 };
 typedef MoeSkinnyArgsT<SkinnyArgs> MoeSkinnyArgs;
 
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(256) void moe_skinny_kernel(MoeSkinnyArgsT<typename
     if (cnt > q.R - row0) cnt = q.R - row0;
     if (cnt <= 0) return;                                  // an idle expert: no weight load
     typename WF::Args p = q.g;
-    WF::at_expert(p, e, q.w_stride);
+    WF::at_expert(p, e, q.w_stride, q.s_stride);
     bf16_t* xs = (bf16_t*)vl2_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.x * 64 + wave * 16;

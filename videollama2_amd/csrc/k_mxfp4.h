@@ -210,6 +210,11 @@ struct SkinnyWMx4 {
         return word{__builtin_nontemporal_load((const uint32_t*)(wrow + (kc >> 1) + s * 16)), srow[(kc >> 5) + s]};
     }
     static __device__ __forceinline__ bf16x8 frag(word w) { return __builtin_bit_cast(bf16x8, mx4_cvt8(w.q, mx4_scale(w.s))); }
+    // the grouped form (k_moe_skinny.h, k_moe_mxfp4.h): expert e's codes and scales, q_stride / s_stride bytes apart
+    static __device__ __forceinline__ void at_expert(Args& p, int e, long long q_stride, long long s_stride) {
+        p.Q += (size_t)e * q_stride;
+        p.S += (size_t)e * s_stride;
+    }
 };
 
 template <int MT>

@@ -35,8 +35,9 @@ struct SkinnyWBf16 {
     __device__ __forceinline__ SkinnyWBf16(const Args& p, int n, int k0, int lg) : wrow(p.W + (size_t)n * p.ldw + k0 + lg * 8) {}
     __device__ __forceinline__ word load(int kc, int s) const { return __builtin_nontemporal_load((const u32x4*)(wrow + kc + s * 32)); }
     static __device__ __forceinline__ bf16x8 frag(word w) { return __builtin_bit_cast(bf16x8, w); }
-    // the grouped form (k_moe_skinny.h): the arguments of expert e of a stack whose matrices lie `stride` elements apart
-    static __device__ __forceinline__ void at_expert(Args& p, int e, long long stride) { p.W += (size_t)e * stride; }
+    // the grouped form (k_moe_skinny.h): the arguments of expert e of a stack whose matrices lie `stride` elements apart (the second stride
+    // is for a format with a second array per expert, k_mxfp4.h)
+    static __device__ __forceinline__ void at_expert(Args& p, int e, long long stride, long long) { p.W += (size_t)e * stride; }
 };
 
 // THE skinny-M body of every weight format: grid = (N/64, KS), block 256; dynamic LDS = Mp * (kchunk + 8) * 2 bytes.  The grid, the K

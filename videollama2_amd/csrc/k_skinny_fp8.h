@@ -42,7 +42,7 @@ struct SkinnyWFp8 {
     __device__ __forceinline__ SkinnyWFp8(const Args& p, int n, int k0, int lg) : wrow(p.Q + (size_t)n * p.ldq + k0 + lg * 8) {}
     __device__ __forceinline__ word load(int kc, int s) const { return __builtin_nontemporal_load((const u32x2*)(wrow + kc + s * 32)); }
     static __device__ __forceinline__ bf16x8 frag(word w) { return fp8x8_to_frag(w); }
-    static __device__ __forceinline__ void at_expert(Args& p, int e, long long stride) { p.Q += (size_t)e * stride; }
+    static __device__ __forceinline__ void at_expert(Args& p, int e, long long stride, long long) { p.Q += (size_t)e * stride; }
 };
 
 template <int MT>

@@ -39,6 +39,7 @@ static constexpr bool kLab = false;
 #include "k_moe.h"
 #include "k_moe_skinny.h"
 #include "k_moe_fp8.h"
+#include "k_moe_mxfp4.h"
 #include "k_moe_gemm8.h"
 #include "k_attn_append.h"
 #include "k_attn_shared.h"
@@ -1801,6 +1802,103 @@ extern "C" int32_t vl2_moe_gemm_fp8(const void* A, int32_t lda, const void* q, i
     if (sw) launch<moe_gemm8_kernel<true>>(grid, dim3(512), MOE8_LDS_BYTES, s, m);
     else launch<moe_gemm8_kernel<false>>(grid, dim3(512), MOE8_LDS_BYTES, s, m);
     return launched("vl2_moe_gemm_fp8");
+}
+
+// ------------------------------------------------------------------------------------------------ MXFP4 expert weights of the MoE decode, k_moe_mxfp4.h
+// ONE host routine behind vl2_moe_gemv_mxfp4 (S = 1, the rows' strides their widths) and vl2_moe_gemv_batched_mxfp4.  Every check precedes every
+// launch.  No tiled W4A16 grouped GEMM is built: vl2_moe_gemm_skinny_mxfp4 (S <= 64) is the only grouped form.
+static int32_t moe_gemv_mxfp4_rows(const char* who, const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride, int32_t lds_,
+                                   const void* x, int32_t ldx, const int32_t* ids, const float* wts, const void* res, int32_t ldres, void* y, int32_t ldy,
+                                   int32_t S, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "%s: null q (the experts' E2M1 codes)", who);
+    if (!scale) return fail(VL2_E_BADARG, "%s: null scale (the experts' E8M0 block scales)", who);
+    if (!x || !ids || !y || S <= 0 || E <= 0 || k <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "%s: null pointer or empty shape", who);
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "%s: need E <= %d and 1 <= k <= min(E, %d)", who, MOE_MAX_E, MOE_MAX_K);
+    if (S > 65535) return fail(VL2_E_SHAPE, "%s: S=%d tokens exceed the grid", who, S);
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "%s: flags other than VL2_GEMM_SWIGLU not built", who);
+    if (K % 32) return fail(VL2_E_SHAPE, "%s: need K%%32==0 (one scale per block of 32; K=%d)", who, K);
+    if (K > 32704) return fail(VL2_E_SHAPE, "%s: need K<=32704 (x lives in LDS as 16-bit elements; K=%d)", who, K);
+    if (ldq % 16 || ldq < K / 2 || lds_ < K / 32 || q_stride % 16 || q_stride < (int64_t)N * ldq || s_stride < (int64_t)N * lds_ || ldx % 8 || ldx < K ||
+        !ALIGNED16(q) || !ALIGNED16(x))
+        return fail(VL2_E_SHAPE, "%s: need 16-byte aligned rows, ldq%%16==0, ldq >= K/2, lds >= K/32, ldx >= K, q_stride%%16==0, q_stride >= N*ldq, s_stride >= N*lds", who);
+    hipStream_t s = ST(stream);
+    if (flags & VL2_GEMM_SWIGLU) {       // x [S, ldx] -> y [S * k, ldy]
+        if (N % 64 || wts || res || ldy < N / 2) return fail(VL2_E_SHAPE, "%s: SWIGLU needs N%%64==0, ldy >= N/2 and no wts / res (N=%d)", who, N);
+        Gemv4Args a{(const uint8_t*)q, (const uint8_t*)scale, (const bf16_t*)x, nullptr, nullptr, y, N, K, ldq, lds_, eps, nullptr, 1, 0, 0, 0};
+        const dim3 b(256);
+        // launch_gemv_mxfp4_rows' rule: rows of K <= 4096 run four pairs per wave and trip
+        if (K <= 4096)
+            hipLaunchKernelGGL(moe_gemv_gu_mxfp4_kernel<4>, dim3((N / 2 + 15) / 16, k, S), b, (size_t)K * 2, s, a, (const int*)ids, (long long)q_stride,
+                               (long long)s_stride, E, ldy, ldx);
+        else
+            hipLaunchKernelGGL(moe_gemv_gu_mxfp4_kernel<1>, dim3((N / 2 + 3) / 4, k, S), b, (size_t)K * 2, s, a, (const int*)ids, (long long)q_stride,
+                               (long long)s_stride, E, ldy, ldx);
+        return launched(who);
+    }
+    if (!wts) return fail(VL2_E_BADARG, "%s: the down form needs the routing weights", who);
+    if (ldx != K) return fail(VL2_E_SHAPE, "%s: the down form reads the SwiGLU rows [S * k, K] without a gap (ldx=%d K=%d)", who, ldx, K);
+    if (ldy < N || (res && ldres < N)) return fail(VL2_E_SHAPE, "%s: need ldy / ldres >= N (N=%d)", who, N);
+    const size_t lds = (size_t)k * K * 2;
+    if (lds > 160 * 1024) return fail(VL2_E_SHAPE, "%s: k * K * 2 bytes of activations must fit the LDS (k=%d K=%d)", who, k, K);
+    const dim3 g((N + 3) / 4, S), b(256);
+#define VL2_MOE_DOWN4(KS) do { lds_attr<moe_gemv_down_mxfp4_kernel<KS>>(160 * 1024); \
+        hipLaunchKernelGGL((moe_gemv_down_mxfp4_kernel<KS>), g, b, lds, s, (const uint8_t*)q, (long long)q_stride, ldq, (const uint8_t*)scale, \
+                           (long long)s_stride, lds_, (const bf16_t*)x, (const int*)ids, wts, (const bf16_t*)res, ldres, (bf16_t*)y, ldy, N, K, E); } while (0)
+    if (k == 1) VL2_MOE_DOWN4(1); else if (k == 2) VL2_MOE_DOWN4(2); else if (k == 3) VL2_MOE_DOWN4(3); else VL2_MOE_DOWN4(4);
+#undef VL2_MOE_DOWN4
+    return launched(who);
+}
+extern "C" int32_t vl2_moe_gemv_mxfp4(const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride, int32_t lds, const void* x,
+                                      const int32_t* ids, const float* wts, const void* res, void* y, int32_t E, int32_t k, int32_t N, int32_t K, float eps,
+                                      int32_t flags, void* stream) {
+    const int n_out = (flags & VL2_GEMM_SWIGLU) ? N / 2 : N;
+    return moe_gemv_mxfp4_rows("vl2_moe_gemv_mxfp4", q, q_stride, ldq, scale, s_stride, lds, x, K, ids, wts, res, n_out, y, n_out, 1, E, k, N, K, eps, flags,
+                               stream);
+}
+extern "C" int32_t vl2_moe_gemv_batched_mxfp4(const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride, int32_t lds, const void* x,
+                                              int32_t ldx, const int32_t* ids, const float* wts, const void* res, int32_t ldres, void* y, int32_t ldy,
+                                              int32_t S, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream) {
+    return moe_gemv_mxfp4_rows("vl2_moe_gemv_batched_mxfp4", q, q_stride, ldq, scale, s_stride, lds, x, ldx, ids, wts, res, ldres, y, ldy, S, E, k, N, K, eps,
+                               flags, stream);
+}
+extern "C" int32_t vl2_moe_gemm_skinny_mxfp4(const void* A, int32_t lda, int32_t a_rows, const int32_t* rowmap, const void* q, int64_t q_stride, int32_t ldq,
+                                             const void* scale, int64_t s_stride, int32_t lds_, void* C, int32_t ldc, const int32_t* counts,
+                                             const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t N, int32_t K, int32_t flags, void* part,
+                                             int64_t part_bytes, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny_mxfp4: null q (the experts' E2M1 codes)");
+    if (!scale) return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny_mxfp4: null scale (the experts' E8M0 block scales)");
+    if (!A || !C || !counts || !offs || S <= 0 || k <= 0 || E <= 0 || N <= 0 || K <= 0 || a_rows <= 0)
+        return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny_mxfp4: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_skinny_mxfp4: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (S > 64) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny_mxfp4: S=%d tokens, need S<=64 (no tiled W4A16 grouped GEMM is built)", S);
+    const bool sw = flags & VL2_GEMM_SWIGLU;
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_skinny_mxfp4: flags other than VL2_GEMM_SWIGLU not built");
+    if (N % 64 || (sw && N % 128)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny_mxfp4: need N%%64==0 (N%%128==0 with SWIGLU; N=%d)", N);
+    if (K % 32 || K > 32704) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny_mxfp4: need K%%32==0, K<=32704 (K=%d)", K);
+    const int R = S * k;
+    if (lda % 8 || ldq % 16 || ldc % 4 || lda < K || ldq < K / 2 || lds_ < K / 32 || q_stride % 16 || q_stride < (int64_t)N * ldq ||
+        s_stride < (int64_t)N * lds_ || ldc < (sw ? N / 2 : N) || !ALIGNED16(A) || !ALIGNED16(q) || (((uintptr_t)C) & 7))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny_mxfp4: need 16-byte aligned rows, lda%%8==0, ldq%%16==0, ldc%%4==0, lda >= K, ldq >= K/2, lds >= K/32, q_stride%%16==0, q_stride >= N*ldq, s_stride >= N*lds");
+    if (a_rows < (rowmap ? S : R)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny_mxfp4: A has %d rows, need %d", a_rows, rowmap ? S : R);
+    if (!part || !ALIGNED16(part) || part_bytes <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny_mxfp4: needs a 16-byte aligned buffer of fp32 partial sums");
+    SkinnyPlan pl;
+    if (moe_skinny_plan(S, N, K, pl) != SKINNY_PLAN_OK) return fail(VL2_E_SHAPE, "vl2_moe_gemm_skinny_mxfp4: no K chunking for K=%d", K);
+    const int64_t need = (int64_t)pl.ks * R * N * 4;
+    if (need > part_bytes)
+        return fail(VL2_E_BADARG, "vl2_moe_gemm_skinny_mxfp4: partial buffer too small (%lld bytes, need %lld: the K split is never shrunk)", (long long)part_bytes, (long long)need);
+    MoeSkinnyArgsT<Skinny4Args> a{};
+    a.g = Skinny4Args{(const bf16_t*)A, (const uint8_t*)q, (const uint8_t*)scale, (float*)part, S, N, K, lda, ldq, lds_, pl.kslice, pl.kchunk};
+    a.counts = counts; a.offs = offs; a.rowmap = rowmap; a.w_stride = q_stride; a.s_stride = s_stride; a.R = R; a.a_rows = a_rows;
+    hipStream_t s = ST(stream);
+    const dim3 gk(N / 64, pl.ks, E), b(256);
+    if (pl.mt == 1) { lds_attr<moe_skinny_kernel<1, SkinnyWMx4>>(65536); hipLaunchKernelGGL((moe_skinny_kernel<1, SkinnyWMx4>), gk, b, pl.lds, s, a); }
+    else if (pl.mt == 2) { lds_attr<moe_skinny_kernel<2, SkinnyWMx4>>(65536); hipLaunchKernelGGL((moe_skinny_kernel<2, SkinnyWMx4>), gk, b, pl.lds, s, a); }
+    else { lds_attr<moe_skinny_kernel<4, SkinnyWMx4>>(65536); hipLaunchKernelGGL((moe_skinny_kernel<4, SkinnyWMx4>), gk, b, pl.lds, s, a); }
+    SkinnyReduceArgs r{(const float*)part, C, nullptr, nullptr, R, R, N, pl.ks, ldc, 0, nullptr};
+    const dim3 g((R * ((sw ? N / 2 : N) / 4) + 255) / 256);
+    if (sw) hipLaunchKernelGGL(moe_skinny_reduce_mxfp4_kernel<true>, g, b, 0, s, r, (const int*)counts, (const int*)offs, E);
+    else hipLaunchKernelGGL(moe_skinny_reduce_mxfp4_kernel<false>, g, b, 0, s, r, (const int*)counts, (const int*)offs, E);
+    return launched("vl2_moe_gemm_skinny_mxfp4");
 }
 
 #include "vl2_stage.inc"

@@ -1131,7 +1131,8 @@ class HipMixtralDecoder(HipMistralDecoder):
     dense-only); every routing table stays on the device, so the prefill and the decode step both capture into graphs.
     Single GPU, 16-bit weights: tensor parallelism and fp8 weights raise NotImplementedError, and so does batched / continuous decoding
     until `enable_moe_batch()` switches it on.  `enable_moe_fp8()` is this decoder's own fp8 switch: the decode
-    step's expert products on e4m3fn copies of the expert stacks, everything else 16-bit."""
+    step's expert products on e4m3fn copies of the expert stacks, everything else 16-bit.  `enable_moe_mxfp4()` is
+    the same switch for OCP MXFP4 copies (4.25 bits per weight); the two exclude each other."""
 
     def __init__(self, cfg, state_dict, device="cuda", max_seq_len=4096, n_layers=None, tp_group=None, tp_shard=None, tp_local=None):
         if tp_group is not None or tp_shard is not None or tp_local is not None:
@@ -1234,10 +1235,51 @@ class HipMixtralDecoder(HipMistralDecoder):
         busy = getattr(self, "_bb_busy", None)
         if busy is not None and busy.in_flight():
             raise RuntimeError("enable_moe_fp8: a ContinuousBatcher holds requests in flight on this decoder's slots: drain it (run()) first")
+        if on and self.moe_mxfp4:
+            raise ValueError("MXFP4 expert weights are on: call enable_moe_mxfp4(False) before enable_moe_fp8()")
         if on and getattr(self, "w8moe", None) is None:
             self.w8moe = [dict(wgu=ops.moe_quant_fp8(lw["wgu"]), wd=ops.moe_quant_fp8(lw["wd"])) for lw in self.w["layers"]]
         self._moe_fp8 = bool(on)
         self._moe_fp8_tiled = bool(on and tiled)
+        self._invalidate_graphs()
+        self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
+        return self
+
+    MOE_MXFP4_ROWS = 64     # the most sequences of a batched step while enable_moe_mxfp4 is on: the grouped skinny-M GEMM's limit (no tiled W4A16
+    #                         grouped GEMM is built, and the 16-bit tiled form would change a request's arithmetic with the batch size)
+
+    @property
+    def moe_mxfp4(self):
+        """Whether the decode step's expert products stream MXFP4 copies of the expert weights (enable_moe_mxfp4)."""
+        return getattr(self, "_moe_mxfp4", False)
+
+    def _moe_mxfp4_limit(self, got):
+        return NotImplementedError(f"MoE (mixtral) decoder: MXFP4 expert weights are on (enable_moe_mxfp4): a batched step takes at most "
+                                   f"{self.MOE_MXFP4_ROWS} sequences, the grouped skinny-M GEMM's limit (no tiled W4A16 grouped GEMM is built); "
+                                   f"got {got}")
+
+    @torch.no_grad()
+    def enable_moe_mxfp4(self, on=True):
+        """OPTIONAL arithmetic, never the default: every expert product of the decode step -- the solo step, and with
+        enable_moe_batch() the batched and continuous steps -- reads OCP MXFP4 copies of wgu [E, 2I, D] and wd [E, D, I]: E2M1 codes with one
+        E8M0 scale per block of 32 k, 4.25 bits per weight (ops.moe_quant_mxfp4, the quantiser of tests/mxfp4_oracle.py); activations stay
+        16-bit, products and sums fp32, the block scale rides in the conversion (W4A16, csrc/k_moe_mxfp4.h).  The prefill, the router,
+        attention, RoPE, the KV cache, wqkv / wo and lm_head keep their 16-bit weights, so `decode_format` stays "16bit" and
+        enable_fp8_decode / enable_fp8_prefill / enable_mxfp4_decode keep refusing.  The copies are made once, here (computed: E * 3 * I * D *
+        32 layers * 4.25 / 8 bytes = +24 GB beside the 93 GB of 16-bit weights for the 8x7B model at full depth; the prefill still reads the
+        latter).  A batched step runs the MXFP4 rows kernels below MOE_GEMM_BATCH sequences and the MXFP4 grouped skinny-M GEMM from there to
+        MOE_MXFP4_ROWS = 64; more slots than that are refused: no tiled W4A16 grouped GEMM is built, and the 16-bit tiled form is never used
+        while the switch is on (a request's arithmetic may change with the batch size by summation order only).  enable_moe_fp8 and this
+        switch refuse each other while the other is on.  Switching drops the captured graphs and bumps cache_epoch; it is refused while a
+        batcher holds requests in flight."""
+        busy = getattr(self, "_bb_busy", None)
+        if busy is not None and busy.in_flight():
+            raise RuntimeError("enable_moe_mxfp4: a ContinuousBatcher holds requests in flight on this decoder's slots: drain it (run()) first")
+        if on and self.moe_fp8:
+            raise ValueError("fp8 expert weights are on: call enable_moe_fp8(False) before enable_moe_mxfp4()")
+        if on and getattr(self, "w4moe", None) is None:
+            self.w4moe = [dict(wgu=ops.moe_quant_mxfp4(lw["wgu"]), wd=ops.moe_quant_mxfp4(lw["wd"])) for lw in self.w["layers"]]
+        self._moe_mxfp4 = bool(on)
         self._invalidate_graphs()
         self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
         return self
@@ -1293,6 +1335,8 @@ class HipMixtralDecoder(HipMistralDecoder):
             raise NotImplementedError(f"MoE (mixtral) decoder: fp8 expert weights are on (enable_moe_fp8): a batched step takes at most "
                                       f"{self.MOE_FP8_ROWS} sequences, the grouped skinny-M GEMM's limit (no tiled W8A16 grouped GEMM is built); "
                                       f"got {B}")
+        if self.moe_mxfp4 and B > self.MOE_MXFP4_ROWS:
+            raise self._moe_mxfp4_limit(B)
         bb = super()._ensure_batch(B, owner)
         if "moe" not in bb:
             bb["moe"] = self._moe_step_buffers(bb["B"])
@@ -1334,6 +1378,11 @@ class HipMixtralDecoder(HipMistralDecoder):
             ops.moe_gemv_fp8(*w8["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
             ops.moe_gemv_fp8(*w8["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
             return
+        if self.moe_mxfp4:                       # the same two launches on the MXFP4 copies (enable_moe_mxfp4)
+            w4 = self.w4moe[li]
+            ops.moe_gemv_mxfp4(*w4["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
+            ops.moe_gemv_mxfp4(*w4["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
+            return
         ops.moe_gemv(lw["wgu"], x1, self.moe_ids, swiglu=True, eps=self.eps, out=a)
         ops.moe_gemv(lw["wd"], a, self.moe_ids, wts=self.moe_wts, res=x1, out=x)
 
@@ -1364,6 +1413,25 @@ class HipMixtralDecoder(HipMistralDecoder):
         ops.moe_combine(x1, m["y"][:R], t, self.eps, out=x)
         return ids, wts
 
+    def _token_block_batched_mxfp4(self, w4, lw, x, x1, nb, m, ids, wts):
+        """The MoE block of a batched step on the MXFP4 expert copies: the rows kernels below MOE_GEMM_BATCH (a row is bit for bit the solo
+        MXFP4 step), the grouped skinny-M GEMM from there to MOE_MXFP4_ROWS (the solo MXFP4 step up to summation order).  No tiled W4A16
+        grouped GEMM is built: more rows are refused."""
+        if nb > self.MOE_MXFP4_ROWS:
+            raise self._moe_mxfp4_limit(nb)
+        k, R = self.k, nb * self.k
+        if nb < self.MOE_GEMM_BATCH:
+            ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
+            ops.moe_gemv_batched_mxfp4(*w4["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])
+            ops.moe_gemv_batched_mxfp4(*w4["wd"], m["a"][:R], ids, wts=wts, res=x1, out=x)
+            return
+        t = dict(counts=m["counts"], offs=m["offs"], gather=m["gather"][:R], inv=m["inv"][:nb], wts=wts)
+        ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts, tables=t)
+        h = ops.rmsnorm(x1, self.w["ones"], self.eps, out=m["h"][:nb])              # (the norm weight is folded into wgu)
+        ops.moe_gemm_skinny_mxfp4(h, *w4["wgu"], t, nb, k, m["part"], rowmap=t["gather"], swiglu=True, out=m["a"][:R])
+        ops.moe_gemm_skinny_mxfp4(m["a"][:R], *w4["wd"], t, nb, k, m["part"], out=m["y"][:R])
+        ops.moe_combine(x1, m["y"][:R], t, self.eps, out=x)
+
     def _token_block_batched(self, f, lw, o, x, x1, li=None):
         """The same for the nb rows of a batched step (enable_moe_batch), on the slot buffers' MoE tensors: x1 = x + o_proj(o) through the
         form, then one of three regimes by nb (class attributes MOE_GEMM_BATCH / MOE_SKINNY_ROWS).  No host read and, in the first two, no
@@ -1374,6 +1442,8 @@ class HipMixtralDecoder(HipMistralDecoder):
         ids, wts = m["ids"][:nb], m["wts"][:nb]
         if self.moe_fp8:                         # (enable_moe_fp8: the 16-bit regimes below are untouched with the switch off)
             ids, wts = self._token_block_batched_fp8(self.w8moe[li], lw, x, x1, nb, m, ids, wts)
+        elif self.moe_mxfp4:                     # (enable_moe_mxfp4: likewise)
+            self._token_block_batched_mxfp4(self.w4moe[li], lw, x, x1, nb, m, ids, wts)
         elif nb < self.MOE_GEMM_BATCH:             # the solo step's GEMVs, a token index in the grid: every (token, slot) pair streams its expert
             ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
             ops.moe_gemv_batched(lw["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])

@@ -454,6 +454,16 @@ class VideoLLaMA2Hip(nn.Module):
         self.decoder.enable_moe_fp8(on, tiled=tiled)
         return self
 
+    def enable_moe_mxfp4(self, on=True):
+        """OPTIONAL arithmetic, Mixtral only, never the default: the decode step's expert products stream OCP MXFP4 copies of the expert
+        weights -- E2M1 codes with one E8M0 scale per 32 k, 4.25 bits per weight (`HipMixtralDecoder.enable_moe_mxfp4`, DESIGN.md section
+        22e).  The prefill, the router, attention, wqkv / wo and lm_head stay 16-bit; with enable_moe_batch() batches of up to 64 requests
+        decode on the same copies (no tiled W4A16 grouped GEMM is built).  It and enable_moe_fp8 exclude each other."""
+        if not hasattr(self.decoder, "enable_moe_mxfp4"):
+            raise NotImplementedError("enable_moe_mxfp4: the decoder is dense (it has no expert weights; enable_mxfp4_decode() is its MXFP4 switch)")
+        self.decoder.enable_moe_mxfp4(on)
+        return self
+
     def batcher(self, max_slots=4, eos_token_id=None, use_graph=None, reserve="whole"):
         """Continuous batching over this model (serving.ModelBatcher): submit (input_ids, images) requests at any time, `step()`
         decodes one token for everything in flight, admission / retirement happen between steps."""

@@ -1342,3 +1342,69 @@ def moe_gemm_fp8(a, q, scale, route, S, k, swiglu=False, row_norm=None, eps=0.0,
     _lib.call("vl2_moe_gemm_fp8", _p(a), a.stride(0), _p(q), q.stride(0), q.stride(1), _p(scale), scale.stride(0), _p(out), out.stride(0),
               _p(row_norm), float(eps), _p(route["counts"]), _p(route["offs"]), S, k, E, P, N, K, GEMM_SWIGLU if swiglu else 0, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ MXFP4 expert weights of the MoE decode, csrc/k_moe_mxfp4.h
+def moe_quant_mxfp4(w):
+    """An expert stack w [E, N, K] (contiguous, 16-bit, K % 32 == 0) -> (q uint8 [E, N, K / 2]: two E2M1 codes per byte, k = 2j in bits 3:0;
+    s uint8 [E, N, K / 32]: one E8M0 scale per block of 32): ONE vl2_pack_quant_mxfp4 call on the [E * N, K] view, so expert e is
+    `quant_mxfp4(w[e])` bit for bit."""
+    _chk(w, _lib.elem_dtype(), "w")
+    E, N, K = w.shape
+    if not w.is_contiguous():
+        raise ValueError("moe_quant_mxfp4: the expert stack must be contiguous (it is quantised as its [E * N, K] view)")
+    q, s = quant_mxfp4(w.view(E * N, K))
+    return q.view(E, N, K // 2), s.view(E, N, K // 32)
+
+
+def _chk_moe4(who, q, s):
+    _chk(q, torch.uint8, "q"); _chk(s, torch.uint8, "s")
+    if q.dim() != 3 or s.dim() != 3 or tuple(s.shape[:2]) != tuple(q.shape[:2]) or s.shape[2] * 16 != q.shape[2] or q.stride(2) != 1 or s.stride(2) != 1:
+        raise ValueError(f"{who}: need q [E, N, K / 2] bytes and s [E, N, K / 32] bytes (moe_quant_mxfp4), got {tuple(q.shape)} and {tuple(s.shape)}")
+    return q.shape[0], q.shape[1], q.shape[2] * 2
+
+
+def moe_gemv_mxfp4(q, s, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
+    """include/vl2hip.h vl2_moe_gemv_mxfp4: `moe_gemv` on the MXFP4 expert stack (q, s) of `moe_quant_mxfp4` (strided views are taken as they
+    are).  swiglu=True: slot j is bit for bit gemv_mxfp4(q[ids[j]], s[ids[j]], x, swiglu=True, rms_plain=True); else out = res + sum_j wts[j] *
+    gemv_mxfp4(.., x[j], out_f32=True) as an fma chain in slot order, rounded once."""
+    E, N, K = _chk_moe4("moe_gemv_mxfp4", q, s)
+    _chk(x, _lib.elem_dtype(), "x"); _chk(res, _lib.elem_dtype(), "res"); _chk(wts, torch.float32, "wts")
+    k = ids.numel()
+    if out is None:
+        out = torch.empty((k, N // 2) if swiglu else (N,), dtype=_lib.elem_dtype(), device=q.device)
+    _lib.call("vl2_moe_gemv_mxfp4", _p(q), q.stride(0), q.stride(1), _p(s), s.stride(0), s.stride(1), _p(x), _p(ids), _p(wts), _p(res), _p(out), E, k,
+              N, K, float(eps), GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
+
+
+def moe_gemv_batched_mxfp4(q, s, x, ids, wts=None, res=None, swiglu=False, eps=1e-5, out=None):
+    """include/vl2hip.h vl2_moe_gemv_batched_mxfp4: `moe_gemv_mxfp4` for the S tokens of ids [S, k] in one launch; a token's rows are its bits."""
+    E, N, K = _chk_moe4("moe_gemv_batched_mxfp4", q, s)
+    _chk(x, _lib.elem_dtype(), "x"); _chk(res, _lib.elem_dtype(), "res"); _chk(wts, torch.float32, "wts")
+    S, k = ids.shape
+    if x.shape[0] < (S if swiglu else S * k) or (res is not None and res.shape[0] < S) or (wts is not None and wts.numel() < S * k):
+        raise ValueError("moe_gemv_batched_mxfp4: x / res / wts are too short for the S tokens of ids")
+    if out is None:
+        out = torch.empty((S * k, N // 2) if swiglu else (S, N), dtype=_lib.elem_dtype(), device=q.device)
+    if out.shape[0] < (S * k if swiglu else S):
+        raise ValueError("moe_gemv_batched_mxfp4: out is too short for the S tokens of ids")
+    _lib.call("vl2_moe_gemv_batched_mxfp4", _p(q), q.stride(0), q.stride(1), _p(s), s.stride(0), s.stride(1), _p(x), x.stride(0), _p(ids), _p(wts),
+              _p(res), 0 if res is None else res.stride(0), _p(out), out.stride(0), S, E, k, N, K, float(eps), GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
+
+
+def moe_gemm_skinny_mxfp4(a, q, s, tables, S, k, part, rowmap=None, swiglu=False, out=None):
+    """include/vl2hip.h vl2_moe_gemm_skinny_mxfp4: `moe_gemm_skinny` on the MXFP4 expert stack (q, s): a permuted row is bit for bit
+    `gemm_skinny_mxfp4` on that one row with its expert's bytes and scales.  part: fp32 buffer of moe_skinny_part_bytes(S, k, N, K)."""
+    E, N, K = _chk_moe4("moe_gemm_skinny_mxfp4", q, s)
+    _chk(a, _lib.elem_dtype(), "a"); _chk(part, torch.float32, "part")
+    R = S * k
+    if out is None:
+        out = torch.empty((R, N // 2 if swiglu else N), dtype=_lib.elem_dtype(), device=a.device)
+    if out.shape[0] < R or (rowmap is not None and rowmap.numel() < R) or tables["counts"].numel() < E or tables["offs"].numel() < E + 1:
+        raise ValueError("moe_gemm_skinny_mxfp4: out / rowmap / tables are too short for S * k rows and E experts")
+    _lib.call("vl2_moe_gemm_skinny_mxfp4", _p(a), a.stride(0), a.shape[0], _p(rowmap), _p(q), q.stride(0), q.stride(1), _p(s), s.stride(0), s.stride(1),
+              _p(out), out.stride(0), _p(tables["counts"]), _p(tables["offs"]), S, k, E, N, K, GEMM_SWIGLU if swiglu else 0, _p(part),
+              part.numel() * 4, _stream())
+    return out
