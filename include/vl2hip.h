@@ -671,8 +671,8 @@ int32_t vl2_moe_gemm_fp8(const void* A, int32_t lda, const void* q, int64_t q_st
  * codes (k = 2j in bits 3:0), expert e at q + e * q_stride bytes; scale [E, N, lds] = E8M0 bytes, one per 32 k, expert e at scale +
  * e * s_stride bytes (ONE vl2_pack_quant_mxfp4 call on the [E * N, K] view makes both).  The three calls mirror their 16-bit namesakes with
  * q / q_stride / ldq / scale / s_stride / lds in place of W / w_stride / ldw.  K % 32 == 0, K <= 32704, ldq % 16 == 0, ldq >= K / 2,
- * lds >= K / 32, q_stride % 16 == 0, q_stride >= N * ldq, s_stride >= N * lds.  No tiled W4A16 grouped GEMM is built: the skinny form
- * (S <= 64) is the only grouped one. */
+ * lds >= K / 32, q_stride % 16 == 0, q_stride >= N * ldq, s_stride >= N * lds.  The skinny form (S <= 64) is the grouped one of these three;
+ * the tiled W4A16 grouped GEMM for any number of tokens is vl2_moe_gemm_mxfp4 below. */
 /* vl2_moe_gemv on MXFP4 experts.  VL2_GEMM_SWIGLU (N % 64 == 0): slot j is bit for bit vl2_gemv_mxfp4(SWIGLU | RMS_PLAIN) on expert ids[j].
  * flags 0 (any N; k * K * 2 bytes must fit the LDS): y[n] = elem(res[n] + o), o = fma(wts[j], d_j, o) in slot order from 0, d_j bit for bit
  * vl2_gemv_mxfp4(VL2_GEMM_OUT_F32)[n] on expert ids[j] and row x[j]. */
@@ -690,6 +690,15 @@ int32_t vl2_moe_gemm_skinny_mxfp4(const void* A, int32_t lda, int32_t a_rows, co
                                   const void* scale, int64_t s_stride, int32_t lds, void* C, int32_t ldc, const int32_t* counts,
                                   const int32_t* offs, int32_t S, int32_t k, int32_t E, int32_t N, int32_t K, int32_t flags, void* part,
                                   int64_t part_bytes, void* stream);
+
+/* ---- tiled W4A16 grouped GEMM on the MXFP4 expert stacks (csrc/k_moe_gemm4.h): vl2_moe_gemm_fp8 with q / q_stride / ldq / scale / s_stride /
+ * lds of the MXFP4 calls above (strides in bytes), any number of tokens.  A permuted row is bit for bit vl2_moe_gemm on the dequantised stack
+ * 2^e * E2M1(q) (the k order of the 16 x 16 x 32 tile is the same; one k-step is one scale block and the scale rides in the conversion).
+ * N % 128 == 0, K % 64 == 0, ldq % 16 == 0, ldq >= K / 2, lds >= K / 32, q_stride % 16 == 0, q_stride >= N * ldq, s_stride >= N * lds, q
+ * 16-byte aligned (scale, lds and s_stride: any alignment); P as for vl2_moe_gemm.  flags: VL2_GEMM_SWIGLU only. */
+int32_t vl2_moe_gemm_mxfp4(const void* A, int32_t lda, const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride,
+                           int32_t lds, void* C, int32_t ldc, const float* row_norm, float eps, const int32_t* counts, const int32_t* offs,
+                           int32_t S, int32_t k, int32_t E, int32_t P, int32_t N, int32_t K, int32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

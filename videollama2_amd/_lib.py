@@ -203,10 +203,14 @@ MOE_MXFP4_SIGNATURES = {
     "vl2_moe_gemm_skinny_mxfp4": [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                   _i64, _vp],
 }
+# the tiled W4A16 grouped GEMM on the MXFP4 expert stacks (include/vl2hip.h vl2_moe_gemm_mxfp4, csrc/k_moe_gemm4.h): a table of its own for the same reason
+MOE_MXFP4_TILED_SIGNATURES = {
+    "vl2_moe_gemm_mxfp4": [_vp, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+}
 EXPORTS = ["vl2_version", "vl2_elem_name", "vl2_last_error_string", "vl2_workspace_bytes", "vl2_vit_workspace_bytes", "vl2_stc_workspace_bytes", "vl2_llm_workspace_bytes", "vl2_dwconv_mean_workspace_bytes", "vl2_attn_append_ws_bytes", "vl2_attn_decode_shared_partial_floats", "vl2_moe_gemm_skinny_part_bytes"] + list(SIGNATURES) + list(MOE_SIGNATURES) + list(APPEND_SIGNATURES) + \
     list(SAMPLE_ROWS_SIGNATURES) + list(FP8_BATCH_SIGNATURES) + list(MXFP4_SIGNATURES) + list(FP8KV_SIGNATURES) + list(SHARED_PREFIX_SIGNATURES) + list(PAGED_KV_SIGNATURES) + \
     list(PAGED_PREFIX_SIGNATURES) + list(PAGED_FP8KV_SIGNATURES) + list(PAGED_SWAP_SIGNATURES) + list(MOE_BATCH_SIGNATURES) + list(MOE_FP8_SIGNATURES) + \
-    list(MOE_FP8_TILED_SIGNATURES) + list(MOE_MXFP4_SIGNATURES)
+    list(MOE_FP8_TILED_SIGNATURES) + list(MOE_MXFP4_SIGNATURES) + list(MOE_MXFP4_TILED_SIGNATURES)
 
 _lib = None
 # ---- element type of the build in use: "bf16" (libvl2hip.so, the default: BASELINE.json configs[1]) or "fp16" (libvl2hip_f16.so = the same
@@ -315,7 +319,8 @@ def load():
             list(FP8KV_SIGNATURES.items()) + list(SHARED_PREFIX_SIGNATURES.items()) + list(PAGED_KV_SIGNATURES.items()) + \
             list(PAGED_PREFIX_SIGNATURES.items()) + list(PAGED_FP8KV_SIGNATURES.items()) + list(PAGED_SWAP_SIGNATURES.items()) + \
             list(MOE_BATCH_SIGNATURES.items()) + list(MOE_FP8_SIGNATURES.items()) + \
-            list(MOE_FP8_TILED_SIGNATURES.items()) + list(MOE_MXFP4_SIGNATURES.items()):
+            list(MOE_FP8_TILED_SIGNATURES.items()) + list(MOE_MXFP4_SIGNATURES.items()) + \
+            list(MOE_MXFP4_TILED_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = _i32
         fn.argtypes = args

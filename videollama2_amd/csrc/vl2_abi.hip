@@ -41,6 +41,7 @@ static constexpr bool kLab = false;
 #include "k_moe_fp8.h"
 #include "k_moe_mxfp4.h"
 #include "k_moe_gemm8.h"
+#include "k_moe_gemm4.h"
 #include "k_attn_append.h"
 #include "k_attn_shared.h"
 #include "k_kv8.h"
@@ -1806,7 +1807,7 @@ extern "C" int32_t vl2_moe_gemm_fp8(const void* A, int32_t lda, const void* q, i
 
 // ------------------------------------------------------------------------------------------------ MXFP4 expert weights of the MoE decode, k_moe_mxfp4.h
 // ONE host routine behind vl2_moe_gemv_mxfp4 (S = 1, the rows' strides their widths) and vl2_moe_gemv_batched_mxfp4.  Every check precedes every
-// launch.  No tiled W4A16 grouped GEMM is built: vl2_moe_gemm_skinny_mxfp4 (S <= 64) is the only grouped form.
+// launch.  vl2_moe_gemm_skinny_mxfp4 (S <= 64) is the grouped form of these three; the tiled W4A16 grouped GEMM is vl2_moe_gemm_mxfp4 below.
 static int32_t moe_gemv_mxfp4_rows(const char* who, const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride, int32_t lds_,
                                    const void* x, int32_t ldx, const int32_t* ids, const float* wts, const void* res, int32_t ldres, void* y, int32_t ldy,
                                    int32_t S, int32_t E, int32_t k, int32_t N, int32_t K, float eps, int32_t flags, void* stream) {
@@ -1899,6 +1900,43 @@ extern "C" int32_t vl2_moe_gemm_skinny_mxfp4(const void* A, int32_t lda, int32_t
     if (sw) hipLaunchKernelGGL(moe_skinny_reduce_mxfp4_kernel<true>, g, b, 0, s, r, (const int*)counts, (const int*)offs, E);
     else hipLaunchKernelGGL(moe_skinny_reduce_mxfp4_kernel<false>, g, b, 0, s, r, (const int*)counts, (const int*)offs, E);
     return launched("vl2_moe_gemm_skinny_mxfp4");
+}
+
+// ------------------------------------------------------------------------------------------------ tiled W4A16 grouped GEMM, k_moe_gemm4.h
+// vl2_moe_gemm on the MXFP4 expert stacks: every check of vl2_moe_gemm, restated for codes and scale bytes, precedes the launch.  The scales
+// travel as 1-byte LDS-DMA pieces: lds and s_stride carry no alignment rule.
+extern "C" int32_t vl2_moe_gemm_mxfp4(const void* A, int32_t lda, const void* q, int64_t q_stride, int32_t ldq, const void* scale, int64_t s_stride,
+                                      int32_t lds_, void* C, int32_t ldc, const float* row_norm, float eps, const int32_t* counts, const int32_t* offs,
+                                      int32_t S, int32_t k, int32_t E, int32_t P, int32_t N, int32_t K, int32_t flags, void* stream) {
+    if (!q) return fail(VL2_E_BADARG, "vl2_moe_gemm_mxfp4: null q (the experts' E2M1 codes)");
+    if (!scale) return fail(VL2_E_BADARG, "vl2_moe_gemm_mxfp4: null scale (the experts' E8M0 block scales)");
+    if (!A || !C || !counts || !offs || S <= 0 || k <= 0 || E <= 0 || N <= 0 || K <= 0) return fail(VL2_E_BADARG, "vl2_moe_gemm_mxfp4: null pointer or empty shape");
+    if (E > MOE_MAX_E || k > MOE_MAX_K || k > E) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_mxfp4: need E <= %d and 1 <= k <= min(E, %d)", MOE_MAX_E, MOE_MAX_K);
+    if (N % GEMM_BN || K % 64 || lda % 8 || ldc % 8 || lda < K || !ALIGNED16(A) || !ALIGNED16(C) || (row_norm && (((uintptr_t)row_norm) & 7)))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm_mxfp4: need N%%%d==0, K%%64==0, 16-byte aligned rows (N=%d K=%d)", GEMM_BN, N, K);
+    if (ldq % 16 || ldq < K / 2 || lds_ < K / 32 || q_stride % 16 || q_stride < (int64_t)N * ldq || s_stride < (int64_t)N * lds_ || !ALIGNED16(q))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm_mxfp4: need 16-byte aligned code rows, ldq%%16==0, ldq >= K/2, lds >= K/32, q_stride%%16==0, q_stride >= N*ldq, "
+                                 "s_stride >= N*lds (ldq=%d lds=%d)", ldq, lds_);
+    if (!moe_rows_ok(S, k, E, P)) return fail(VL2_E_SHAPE, "vl2_moe_gemm_mxfp4: P=%d must be a multiple of %d and >= S*k + E*%d", P, MOE_BM, MOE_BM - 1);
+    if ((int64_t)(GEMM_BM - 1) * lda + K >= ((int64_t)1 << 30) || (int64_t)(GEMM_BN - 1) * ldq + K / 2 >= ((int64_t)1 << 30) ||
+        (int64_t)(GEMM_BN - 1) * lds_ + K / 32 >= ((int64_t)1 << 30))
+        return fail(VL2_E_SHAPE, "vl2_moe_gemm_mxfp4: a tile's rows exceed the kernels' 32-bit buffer offsets");
+    const bool sw = flags & VL2_GEMM_SWIGLU;
+    if (flags & ~VL2_GEMM_SWIGLU) return fail(VL2_E_UNSUPP, "vl2_moe_gemm_mxfp4: flags other than VL2_GEMM_SWIGLU not built");
+    MoeGemm4Args m{};
+    GemmArgs& a = m.g;
+    a.A = (const bf16_t*)A; a.C = C;
+    a.M = P; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc;
+    a.stats_out_np = N / 64; a.stats_in_np = K / 64; a.idx_ld = P;
+    if (row_norm) { a.norm = VL2_NORM_RMS; a.norm_eps = eps; a.row_norm = row_norm; }
+    m.offs = offs; m.counts = counts; m.q = (const uint8_t*)q; m.scale = (const uint8_t*)scale; m.q_stride = q_stride; m.s_stride = s_stride;
+    m.ldq = ldq; m.lds = lds_; m.E = E;
+    m.rt_cap = P / MOE_BM;
+    const dim3 grid((unsigned)(m.rt_cap * (N / GEMM_BN)));
+    hipStream_t s = ST(stream);
+    if (sw) launch<moe_gemm4_kernel<true>>(grid, dim3(512), MOE4_LDS_BYTES, s, m);
+    else launch<moe_gemm4_kernel<false>>(grid, dim3(512), MOE4_LDS_BYTES, s, m);
+    return launched("vl2_moe_gemm_mxfp4");
 }
 
 #include "vl2_stage.inc"

@@ -1245,13 +1245,28 @@ class HipMixtralDecoder(HipMistralDecoder):
         self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
         return self
 
-    MOE_MXFP4_ROWS = 64     # the most sequences of a batched step while enable_moe_mxfp4 is on: the grouped skinny-M GEMM's limit (no tiled W4A16
-    #                         grouped GEMM is built, and the 16-bit tiled form would change a request's arithmetic with the batch size)
+    MOE_MXFP4_ROWS = 64     # the most sequences of a batched step while enable_moe_mxfp4 is on WITHOUT tiled=True: the grouped skinny-M GEMM's
+    #                         limit (the 16-bit tiled form would change a request's arithmetic with the batch size; the tiled W4A16 grouped
+    #                         GEMM, csrc/k_moe_gemm4.h, serves any number of sequences behind enable_moe_mxfp4(tiled=True))
+    # With enable_moe_mxfp4(tiled=True): from this many sequences on the MXFP4 step runs the tiled W4A16 grouped GEMM (ops.moe_gemm_mxfp4), below
+    # it the MXFP4 grouped skinny-M GEMM.  The rule is MOE_FP8_TILED_FROM's: the smallest measured size from which the tiled MXFP4 step is faster
+    # than the MXFP4 skinny step at that size and at every larger measured size by more than twice the spread of the 16-bit step timed twice;
+    # 65 if there is none (tiled then serves only what was refused before).  Measured (scripts/moe_mxfp4_tiled_bench.py,
+    # profiles/r25_moe_mxfp4_tiled_bench.jsonl; ms per 8-layer step, skinny / tiled, spread <= 0.003 ms): 5: 4.62 / 3.17,
+    # 6: 4.83 / 3.25, 8: 5.27 / 3.40, 12: 5.70 / 3.58, 16: 6.05 / 3.69, 24: 6.71 / 3.91, 32: 7.08 / 4.07, 48: 8.35 / 4.42, 64: 8.92 / 4.72 -- the
+    # tiled form wins at every measured size, so the MXFP4 skinny form serves no size under tiled=True (the value is clamped to MOE_GEMM_BATCH:
+    # the rows kernels keep the sizes below it)
+    MOE_MXFP4_TILED_FROM = 5
 
     @property
     def moe_mxfp4(self):
         """Whether the decode step's expert products stream MXFP4 copies of the expert weights (enable_moe_mxfp4)."""
         return getattr(self, "_moe_mxfp4", False)
+
+    @property
+    def moe_mxfp4_tiled(self):
+        """Whether the batched MXFP4 step may run the tiled W4A16 grouped GEMM (enable_moe_mxfp4(tiled=True))."""
+        return getattr(self, "_moe_mxfp4_tiled", False)
 
     def _moe_mxfp4_limit(self, got):
         return NotImplementedError(f"MoE (mixtral) decoder: MXFP4 expert weights are on (enable_moe_mxfp4): a batched step takes at most "
@@ -1259,7 +1274,7 @@ class HipMixtralDecoder(HipMistralDecoder):
                                    f"got {got}")
 
     @torch.no_grad()
-    def enable_moe_mxfp4(self, on=True):
+    def enable_moe_mxfp4(self, on=True, tiled=False):
         """OPTIONAL arithmetic, never the default: every expert product of the decode step -- the solo step, and with
         enable_moe_batch() the batched and continuous steps -- reads OCP MXFP4 copies of wgu [E, 2I, D] and wd [E, D, I]: E2M1 codes with one
         E8M0 scale per block of 32 k, 4.25 bits per weight (ops.moe_quant_mxfp4, the quantiser of tests/mxfp4_oracle.py); activations stay
@@ -1268,10 +1283,14 @@ class HipMixtralDecoder(HipMistralDecoder):
         enable_fp8_decode / enable_fp8_prefill / enable_mxfp4_decode keep refusing.  The copies are made once, here (computed: E * 3 * I * D *
         32 layers * 4.25 / 8 bytes = +24 GB beside the 93 GB of 16-bit weights for the 8x7B model at full depth; the prefill still reads the
         latter).  A batched step runs the MXFP4 rows kernels below MOE_GEMM_BATCH sequences and the MXFP4 grouped skinny-M GEMM from there to
-        MOE_MXFP4_ROWS = 64; more slots than that are refused: no tiled W4A16 grouped GEMM is built, and the 16-bit tiled form is never used
-        while the switch is on (a request's arithmetic may change with the batch size by summation order only).  enable_moe_fp8 and this
-        switch refuse each other while the other is on.  Switching drops the captured graphs and bumps cache_epoch; it is refused while a
-        batcher holds requests in flight."""
+        MOE_MXFP4_ROWS = 64; more slots than that are refused without tiled=True, and the 16-bit tiled form is never used while the switch is
+        on (a request's arithmetic may change with the batch size by summation order only).
+        tiled=True adds a third regime: from MOE_MXFP4_TILED_FROM sequences on, for any number of them, the prefill's
+        sparse block on the MXFP4 stacks -- ops.moe_route, the tiled W4A16 grouped GEMM ops.moe_gemm_mxfp4 (csrc/k_moe_gemm4.h) twice,
+        ops.moe_combine -- so more than 64 slots are admitted.  Both grouped forms are W4A16 on the same bytes: a request's arithmetic still
+        changes with the batch size by summation order only.
+        enable_moe_fp8 and this switch refuse each other while the other is on.  Switching `on` or `tiled` drops the captured graphs and
+        bumps cache_epoch; it is refused while a batcher holds requests in flight."""
         busy = getattr(self, "_bb_busy", None)
         if busy is not None and busy.in_flight():
             raise RuntimeError("enable_moe_mxfp4: a ContinuousBatcher holds requests in flight on this decoder's slots: drain it (run()) first")
@@ -1280,6 +1299,7 @@ class HipMixtralDecoder(HipMistralDecoder):
         if on and getattr(self, "w4moe", None) is None:
             self.w4moe = [dict(wgu=ops.moe_quant_mxfp4(lw["wgu"]), wd=ops.moe_quant_mxfp4(lw["wd"])) for lw in self.w["layers"]]
         self._moe_mxfp4 = bool(on)
+        self._moe_mxfp4_tiled = bool(on and tiled)
         self._invalidate_graphs()
         self.cache_epoch = getattr(self, "cache_epoch", 0) + 1
         return self
@@ -1335,7 +1355,7 @@ class HipMixtralDecoder(HipMistralDecoder):
             raise NotImplementedError(f"MoE (mixtral) decoder: fp8 expert weights are on (enable_moe_fp8): a batched step takes at most "
                                       f"{self.MOE_FP8_ROWS} sequences, the grouped skinny-M GEMM's limit (no tiled W8A16 grouped GEMM is built); "
                                       f"got {B}")
-        if self.moe_mxfp4 and B > self.MOE_MXFP4_ROWS:
+        if self.moe_mxfp4 and not self.moe_mxfp4_tiled and B > self.MOE_MXFP4_ROWS:
             raise self._moe_mxfp4_limit(B)
         bb = super()._ensure_batch(B, owner)
         if "moe" not in bb:
@@ -1415,8 +1435,15 @@ class HipMixtralDecoder(HipMistralDecoder):
 
     def _token_block_batched_mxfp4(self, w4, lw, x, x1, nb, m, ids, wts):
         """The MoE block of a batched step on the MXFP4 expert copies: the rows kernels below MOE_GEMM_BATCH (a row is bit for bit the solo
-        MXFP4 step), the grouped skinny-M GEMM from there to MOE_MXFP4_ROWS (the solo MXFP4 step up to summation order).  No tiled W4A16
-        grouped GEMM is built: more rows are refused."""
+        MXFP4 step), the grouped skinny-M GEMM from there to MOE_MXFP4_ROWS (the solo MXFP4 step up to summation order; more rows are
+        refused); with enable_moe_mxfp4(tiled=True) the tiled W4A16 grouped GEMM from MOE_MXFP4_TILED_FROM on, for any nb (the same, up to
+        summation order).  Returns the (ids, wts) the block routed with."""
+        if self.moe_mxfp4_tiled and nb >= max(self.MOE_MXFP4_TILED_FROM, self.MOE_GEMM_BATCH):
+            k = self.k
+            r = ops.moe_route(x1, lw["wr"], k, self.eps)    # the prefill's sparse block on the MXFP4 stacks (its tables are sized per call)
+            a = ops.moe_gemm_mxfp4(r["xg"], *w4["wgu"], r, nb, k, swiglu=True, row_norm=r["rn"], eps=self.eps)
+            ops.moe_combine(x1, ops.moe_gemm_mxfp4(a, *w4["wd"], r, nb, k), r, self.eps, out=x)
+            return r["ids"], r["wts"]
         if nb > self.MOE_MXFP4_ROWS:
             raise self._moe_mxfp4_limit(nb)
         k, R = self.k, nb * self.k
@@ -1424,13 +1451,14 @@ class HipMixtralDecoder(HipMistralDecoder):
             ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
             ops.moe_gemv_batched_mxfp4(*w4["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])
             ops.moe_gemv_batched_mxfp4(*w4["wd"], m["a"][:R], ids, wts=wts, res=x1, out=x)
-            return
+            return ids, wts
         t = dict(counts=m["counts"], offs=m["offs"], gather=m["gather"][:R], inv=m["inv"][:nb], wts=wts)
         ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts, tables=t)
         h = ops.rmsnorm(x1, self.w["ones"], self.eps, out=m["h"][:nb])              # (the norm weight is folded into wgu)
         ops.moe_gemm_skinny_mxfp4(h, *w4["wgu"], t, nb, k, m["part"], rowmap=t["gather"], swiglu=True, out=m["a"][:R])
         ops.moe_gemm_skinny_mxfp4(m["a"][:R], *w4["wd"], t, nb, k, m["part"], out=m["y"][:R])
         ops.moe_combine(x1, m["y"][:R], t, self.eps, out=x)
+        return ids, wts
 
     def _token_block_batched(self, f, lw, o, x, x1, li=None):
         """The same for the nb rows of a batched step (enable_moe_batch), on the slot buffers' MoE tensors: x1 = x + o_proj(o) through the
@@ -1443,7 +1471,7 @@ class HipMixtralDecoder(HipMistralDecoder):
         if self.moe_fp8:                         # (enable_moe_fp8: the 16-bit regimes below are untouched with the switch off)
             ids, wts = self._token_block_batched_fp8(self.w8moe[li], lw, x, x1, nb, m, ids, wts)
         elif self.moe_mxfp4:                     # (enable_moe_mxfp4: likewise)
-            self._token_block_batched_mxfp4(self.w4moe[li], lw, x, x1, nb, m, ids, wts)
+            ids, wts = self._token_block_batched_mxfp4(self.w4moe[li], lw, x, x1, nb, m, ids, wts)
         elif nb < self.MOE_GEMM_BATCH:             # the solo step's GEMVs, a token index in the grid: every (token, slot) pair streams its expert
             ops.moe_route_rows(x1, lw["wr"], k, self.eps, ids, wts)
             ops.moe_gemv_batched(lw["wgu"], x1, ids, swiglu=True, eps=self.eps, out=m["a"][:R])

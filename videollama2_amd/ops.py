@@ -1408,3 +1408,18 @@ def moe_gemm_skinny_mxfp4(a, q, s, tables, S, k, part, rowmap=None, swiglu=False
               _p(out), out.stride(0), _p(tables["counts"]), _p(tables["offs"]), S, k, E, N, K, GEMM_SWIGLU if swiglu else 0, _p(part),
               part.numel() * 4, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ tiled W4A16 grouped GEMM, csrc/k_moe_gemm4.h
+def moe_gemm_mxfp4(a, q, s, route, S, k, swiglu=False, row_norm=None, eps=0.0, out=None):
+    """include/vl2hip.h vl2_moe_gemm_mxfp4: `moe_gemm` on the MXFP4 expert stack (q, s) of `moe_quant_mxfp4` (strided views are taken as they
+    are), any number of tokens: the grouped GEMM over the permuted rows a [P, K] (route = moe_route's dict) -> [P, N] (swiglu [P, N/2]); rows
+    of padding are left unwritten.  A row is bit for bit `moe_gemm` on the dequantised stack 2^e * E2M1(q)."""
+    E, N, K = _chk_moe4("moe_gemm_mxfp4", q, s)
+    _chk(a, _lib.elem_dtype(), "a"); _chk(row_norm, torch.float32, "row_norm")
+    P = a.shape[0]
+    if out is None:
+        out = torch.empty((P, N // 2 if swiglu else N), dtype=_lib.elem_dtype(), device=a.device)
+    _lib.call("vl2_moe_gemm_mxfp4", _p(a), a.stride(0), _p(q), q.stride(0), q.stride(1), _p(s), s.stride(0), s.stride(1), _p(out), out.stride(0),
+              _p(row_norm), float(eps), _p(route["counts"]), _p(route["offs"]), S, k, E, P, N, K, GEMM_SWIGLU if swiglu else 0, _stream())
+    return out
